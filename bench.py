@@ -1,6 +1,6 @@
 """bench.py -- contrastive train-step throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: when not already started by torch.distributed.run (no RANK/WORLD_SIZE in the environment) bench.py launches N
 ranks of itself (one per GPU, RCCL over xGMI, rendezvous on 127.0.0.1) and forwards rank 0's JSON line; when the
@@ -21,8 +21,14 @@ Scaling (--scaling): `strong` (default) = the BASELINE configuration: GLOBAL bat
 ranks; `weak` = per-GPU batch fixed at the global batch of the config. With N > 1 and strong scaling the weak-scaling
 throughput is measured as well (fewer steps, after the timed region) and reported under "weak".
 
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps, the outputs of the last timed step
+when --dump-outputs DIR is given (DIR/<name>.npy, see dump_outputs), and the result line (metric, value, unit, higher_is_better,
+dtype, ms_per_step = wall-clock milliseconds per timed step, ...; roofline and cpu_baseline null). Everything else runs only with
+--full: the guarded repeat with SAFE_ROUTES when the default routes fail, the strict-fp32 comparison pass, the weak-scaling pass,
+the tally of the split-operand launches, the per-kernel rooflines, the CPU baseline, the HBM traffic figure and bench_detail.json.
+
 The contract line is the LAST line of stdout and at most 2 KB (the driver keeps a bounded tail of stdout; BENCH_r03 lost its
-head to a 12 KB line). It carries
+head to a 12 KB line). With --full it carries
   roofline      whole step against the roof of THIS implementation: achieved = images/s x TFLOP/image (BASELINE.md section 2,
                 counted on the reference; HIP-event step time) / peak = the same flops with every pipe at its dense peak (split-
                 operand convolutions at 2500 / 3 TFLOP/s for f16x3, the rest at the 157.3 TFLOP/s fp32 MFMA peak); frac = A / P;
@@ -31,8 +37,8 @@ head to a 12 KB line). It carries
   cpu_baseline  N=1, rank 0 only: CPU port of the same train step (same model classes, oracle/cpu_port.py device
                 half) timed on this box's usable host cores on a bounded sample, in a subprocess with a timeout.
 Everything else -- per-kernel rooflines of every hand-written kernel (`kernels`), of every split-operand launch shape of the
-step (`split_kernels`), the strict-fp32 comparison pass, notes -- goes to bench_detail.json (next to bench.py and under
-gpurun_out/ when that exists).
+step (`split_kernels`), the strict-fp32 comparison pass, notes -- goes to bench_detail.json (next to bench.py, and into the
+results folder of the run when there is one; see write_detail).
 """
 import argparse
 import json
@@ -107,6 +113,13 @@ def parse():
     p.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--in-child", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--labels", choices=["uniform", "blocky"], default=None)
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: the guarded repeat with SAFE_ROUTES, the strict-fp32 pass, the weak-scaling "
+                        "pass, the split-operand tally and per-kernel rooflines, the CPU baseline, the traffic figure, bench_detail.json "
+                        "(the --no-* switches still apply)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                        "< 64 MB in all): the loss and the model state it leaves (parameters, gradients, BatchNorm statistics)")
     return p.parse_args()
 
 
@@ -536,6 +549,41 @@ def dominant_kernel(split_rows, arith):
                            "per entry point; in-step durations: profiles/r06_step_steady_kernel_stats.csv"}
 
 
+DUMP_SAMPLE = 4 << 20       # values per dumped array at most (16 MB in float32): larger families are a fixed, seeded sample
+DUMP_SEED = 304
+
+
+def _dump_family(tensors, sample=DUMP_SAMPLE, seed=DUMP_SEED):
+    """Concatenation of the flattened tensors as float32, or -- when longer than `sample` -- its values at a fixed set of
+    positions drawn from `seed` (the same positions from run to run for the same model)."""
+    import numpy as np
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors]) if tensors else torch.zeros(0)
+    if flat.numel() > sample:
+        idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), size=sample))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.cpu().numpy().astype(np.float32)
+
+
+def dump_outputs(out_dir, tr, loss):
+    """--dump-outputs DIR: what the last timed step computed, as a caller of Trainer.train_step receives it -- the loss it returns
+    and the model state it leaves behind. Files (all under 64 MB together):
+      loss.npy     float64 [1]   the loss of the last timed step
+      params.npy   float32       every parameter after the optimizer step (named_parameters order, flattened, concatenated)
+      grads.npy    float32       their gradients from the last backward (zeros where a parameter has none)
+      buffers.npy  float32       the floating-point buffers (BatchNorm running mean / variance, memory banks)
+    A family of more than DUMP_SAMPLE values is stored as the values at a fixed, seeded set of positions (_dump_family)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for _, p in tr.seg_net.named_parameters()]
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    buffers = [b for _, b in tr.seg_net.named_buffers() if b.is_floating_point()]
+    arrays = {"loss": np.array([loss], dtype=np.float64), "params": _dump_family(params), "grads": _dump_family(grads),
+              "buffers": _dump_family(buffers)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return arrays
+
+
 LINE_LIMIT = 2048          # bytes of the contract line: the driver keeps a bounded tail of stdout (BENCH_r03: parsed null at ~12 KB)
 DETAIL_NAME = "bench_detail.json"
 
@@ -550,7 +598,7 @@ def arithmetic_name(Kn, split_on):
 
 
 def assemble_line(args, wl, cfg, world, global_batch, dt, ev_ms, final_loss, split_on, Kn, backend, fp32_pass, weak, cpu,
-                  kernels, split_rows=None, split_flops=0.0):
+                  kernels, split_rows=None, split_flops=0.0, full=True):
     """-> (line, detail). `line` = the ONE JSON line of the contract, at most LINE_LIMIT bytes, printed LAST; `detail` = everything
     else (per-kernel tables, notes, the comparison passes), written to bench_detail.json. Pure function of the measurements:
     exercised on CPU by tests/test_host_surface.py so that a formatting slip cannot cost a GPU run its result.
@@ -559,7 +607,10 @@ def assemble_line(args, wl, cfg, world, global_batch, dt, ev_ms, final_loss, spl
     fp32-equivalent work (HIP-event step time); peak = the rate at which the same flops would run with every pipe at its dense
     peak -- split-operand flops at 2500 / (MFMAs per product) TFLOP/s, the rest at the 157.3 TFLOP/s fp32 MFMA peak -- so
     frac = achieved / peak = roof time / measured time. The figure against the fp32 MFMA peak alone (what a pure fp32
-    implementation is bounded by; can exceed 1) is kept as roofline.vs_fp32_mfma_peak."""
+    implementation is bounded by; can exceed 1) is kept as roofline.vs_fp32_mfma_peak.
+
+    full=False (a plain run, no --full): the roof needs the launch tally and the traffic figure, which only --full takes; the line
+    then carries `roofline` and `cpu_baseline` as null and no `detail`."""
     ips = global_batch * args.steps / dt
     step_ms = ev_ms / args.steps
     ips_ev = global_batch * args.steps / (ev_ms * 1e-3)
@@ -570,7 +621,7 @@ def assemble_line(args, wl, cfg, world, global_batch, dt, ev_ms, final_loss, spl
     rest = total - split
     roof_s = (split / (peak_split_tflops(arith) * 1e12) + rest / (PEAK_FP32_MFMA_TFLOPS * 1e12)) / world
     peak = total / roof_s * 1e-12                                   # TFLOP/s, whole job
-    traffic, traffic_src = step_traffic() if (world == 1 and args.workload == "cfg2") else (None, None)
+    traffic, traffic_src = step_traffic() if (full and world == 1 and args.workload == "cfg2") else (None, None)
     W, H = cfg.get("train", "data_transformer")["input_size"]
     roofline = {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
                 "frac": round(achieved / peak, 4), "traffic": traffic,
@@ -605,6 +656,9 @@ def assemble_line(args, wl, cfg, world, global_batch, dt, ev_ms, final_loss, spl
                    "final_loss": round(final_loss, 5)},
         "roofline": roofline, "cpu_baseline": cpu_short, "detail": DETAIL_NAME,
     }
+    if not full:
+        line.update(roofline=None, cpu_baseline=None)
+        line.pop("detail")
     if fp32_pass is not None and "ms_per_step" in fp32_pass:
         line["fp32_conv_path_ms_per_step"] = fp32_pass["ms_per_step"]
     if weak is not None:
@@ -801,7 +855,7 @@ def self_launch(args):
                          "`--backend gloo` lets ranks share a device for a dry run)\n" % (args.gpus, n_dev))
         sys.exit(2)
     make = lambda attempt: respawn_command(args.gpus, [os.path.abspath(__file__)] + sys.argv[1:])     # fresh port each time
-    if guard_enabled():
+    if args.full and guard_enabled():
         sys.exit(run_guarded(make))
     sys.exit(subprocess.call(make(0), env=dict(os.environ)))
 
@@ -838,7 +892,7 @@ def main():
     from contrastiveseg_amd.lib.utils import distributed as D
     if args.gpus > 1 and not D.launched_by_torchrun():
         self_launch(args)
-    if args.gpus == 1 and not D.launched_by_torchrun() and not args.in_child and guard_enabled():
+    if args.full and args.gpus == 1 and not D.launched_by_torchrun() and not args.in_child and guard_enabled():
         sys.exit(run_guarded(lambda attempt: [sys.executable, os.path.abspath(__file__)] + sys.argv[1:] + ["--in-child"]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -873,6 +927,8 @@ def main():
             and "CSEG_BENCH_ROUTE_FALLBACK" not in os.environ:
         sys.stderr.write("bench.py: non-finite loss %r with the default routes\n" % final_loss)
         sys.exit(3)                                   # the guarding parent repeats the run with SAFE_ROUTES
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, final_loss)   # before anything below runs another step on the same model
     elapsed = torch.tensor([time.perf_counter() - t_start], device=device)
     if world > 1:
         torch.distributed.all_reduce(elapsed, op=torch.distributed.ReduceOp.MAX)      # same decision on every rank
@@ -884,7 +940,7 @@ def main():
     graph_state = os.environ.get("CSEG_STEP_GRAPH_STATE")          # of the TIMED steps (the passes below run eagerly)
     graph_was = step_graph.ENABLED
     step_graph.ENABLED = False            # the comparison pass and the launch tally need the Python path (a replay ignores the switches)
-    if split_on and not args.no_fp32_pass:
+    if args.full and split_on and not args.no_fp32_pass:
         Kn.CONV3X3_SPLIT_BF16 = False
         try:                              # never lose the headline number to the comparison pass
             f_steps = max(3, args.steps // 2)
@@ -899,7 +955,7 @@ def main():
 
     split_flops = 0.0
     tally = None
-    if split_on:
+    if args.full and split_on:
         # one extra untimed step with counting wrappers, on EVERY rank (it contains the step's collectives): which flops run on the
         # split-operand kernels -> the roof of this implementation
         try:
@@ -913,7 +969,7 @@ def main():
     weak = None
     # extra weak-scaling pass: RCCL runs only (the gloo dry run shares one GPU between the ranks and says nothing about
     # scaling), and only when the headline measurement itself was quick, so the whole invocation stays within minutes
-    if (world > 1 and args.scaling == "strong" and not args.no_weak and torch.distributed.get_backend() == "nccl"
+    if (args.full and world > 1 and args.scaling == "strong" and not args.no_weak and torch.distributed.get_backend() == "nccl"
             and float(elapsed) < 180.0):
         # per-GPU work fixed at the config's global batch: separates "the step is too small per GPU" from "the
         # collectives do not overlap". Fewer steps; outside the timed region of the headline number.
@@ -930,7 +986,7 @@ def main():
 
     kernels = None
     split_rows = None
-    if rank == 0 and not args.no_kernels and args.workload == "cfg2":
+    if rank == 0 and args.full and not args.no_kernels and args.workload == "cfg2":
         if world == 1 and split_on and tally is not None:
             try:
                 split_rows, split_flops = split_kernel_rooflines(tally, device, Kn)
@@ -943,7 +999,7 @@ def main():
         except Exception as e:
             kernels = {"error": repr(e)}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
         try:
             cpu = cpu_baseline()
         except Exception as e:
@@ -955,8 +1011,9 @@ def main():
     if rank == 0:
         line, detail = assemble_line(args, wl, cfg, world, global_batch, dt, ev_ms, final_loss, split_on, Kn,
                                      torch.distributed.get_backend() if (world > 1 or args.dist_single_rank) else None, fp32_pass, weak, cpu, kernels,
-                                     split_rows if (split_rows and "error" not in split_rows[0]) else None, split_flops)
-        write_detail(detail)
+                                     split_rows if (split_rows and "error" not in split_rows[0]) else None, split_flops, full=args.full)
+        if args.full:
+            write_detail(detail)
     if world > 1 or args.dist_single_rank:
         try:                                          # every rank empties its C stdio buffers BEFORE rank 0 prints the line
             import ctypes

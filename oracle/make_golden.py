@@ -677,8 +677,82 @@ def run_running_score():
     rs = RunningScore(None, num_classes=K, ignore_index=-1)
     rs.update(pred, true)
     np.savez_compressed(os.path.join(OUT, "running_score.npz"), confusion=rs.confusion_matrix.astype(np.int64),
-                        mean_iou=np.array(rs.get_mean_iou()), pixel_acc=np.array(rs.get_pixel_acc()))
+                        mean_iou=np.array(rs.get_mean_iou()), pixel_acc=np.array(rs.get_pixel_acc()),
+                        mean_acc=np.array(rs.get_mean_acc(), dtype=np.float64),
+                        cls_iou=np.array(list(rs.get_cls_iou().values()), dtype=np.float64))
     print("running_score: mIoU %.6f acc %.6f" % (rs.get_mean_iou(), rs.get_pixel_acc()))
+
+
+def run_state_dicts():
+    """Per model of tests/test_models_vs_reference.py, the reference's state_dict under torch.manual_seed(304) as digests: number
+    of entries, SHA-256 of the [key, shape, dtype] list in order, SHA-256 of all values in order (the checkpoint-interchange test
+    of tests/test_host_surface.py reads the hrnet_w48_contrast layout digest)."""
+    import json
+    import torch
+    ref_shim.install()
+    from lib.models.model_manager import ModelManager as RefManager
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    from test_models_vs_reference import CASES, state_digests
+    out = {}
+    for model, backbone, contrast in CASES:
+        torch.manual_seed(304)
+        sd = RefManager(ref_shim.configer(model_name=model, backbone=backbone, contrast=contrast)).semantic_segmentor().state_dict()
+        n, layout, values = state_digests(sd)
+        out[model] = {"entries": n, "layout_sha256": layout, "values_sha256": values}
+        print("state_dict %s: %d entries" % (model, n))
+    with open(os.path.join(OUT, "ref_state_digests.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
+def run_aug_decisions():
+    """The random decisions of the reference's own transform classes (lib/datasets/tools/cv2_aug_transforms.py, cv2 stubbed)
+    under random.seed(1234) for the sizes of tests/test_gpu_aug_host.py: per sample and transform [name, skipped, arguments,
+    output shape, first output value]."""
+    import collections
+    import collections.abc
+    import importlib
+    import json
+    import random
+    ref_shim.install()
+    cv2 = sys.modules["cv2"]
+    cv2.INTER_CUBIC, cv2.INTER_NEAREST = 2, 0
+    cv2.resize = lambda x, size, interpolation=None: np.full((size[1], size[0]) + x.shape[2:], 128, dtype=x.dtype)
+    cv2.flip = lambda x, code: x
+    if not hasattr(collections, "Iterable"):
+        collections.Iterable = collections.abc.Iterable      # the reference predates Python 3.10 (:519)
+    aug = importlib.import_module("lib.datasets.tools.cv2_aug_transforms")
+    from lib.utils.tools.configer import Configer as RefConfiger
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    from test_gpu_aug_host import AUG_SEED, AUG_SIZES, _configer
+
+    def plain(v):
+        if isinstance(v, (tuple, list)):
+            return [plain(x) for x in v]
+        if isinstance(v, (np.integer, np.bool_)):
+            return v.item()
+        return v
+    log = []
+    orig = aug._BaseTransform._process
+
+    def spy(self, img, data_dict, skip, *args, **kw):
+        out_img, out = orig(self, img, data_dict, skip, *args, **kw)
+        log[-1].append([type(self).__name__, bool(skip), plain(list(args)), list(out_img.shape), int(out_img.reshape(-1)[0])])
+        return out_img, out
+    aug._BaseTransform._process = spy
+    try:
+        compose = aug.CV2AugCompose(_configer(RefConfiger), split="train")
+        random.seed(AUG_SEED)
+        for (w, h) in AUG_SIZES:
+            log.append([])
+            compose(np.full((h, w, 3), 128, np.uint8), labelmap=np.zeros((h, w), np.float32))
+    finally:
+        aug._BaseTransform._process = orig
+    with open(os.path.join(OUT, "aug_decisions.json"), "w") as f:
+        f.write('{"seed": %d, "sizes": %s, "log": [\n' % (AUG_SEED, json.dumps([list(s) for s in AUG_SIZES])))
+        f.write(",\n".join(json.dumps(sample) for sample in log))          # one sample per line
+        f.write("\n]}\n")
+    print("aug_decisions: %d samples" % len(log))
 
 
 def main():
@@ -700,6 +774,10 @@ def main():
             run_step_case(name, c)
     if a.only is None or a.only == "running_score":
         run_running_score()
+    if a.only is None or a.only == "state_dicts":
+        run_state_dicts()
+    if a.only is None or a.only == "aug_decisions":
+        run_aug_decisions()
 
 
 if __name__ == "__main__":

@@ -2,21 +2,22 @@
 contrastiveseg_amd/lib/datasets/tools/gpu_aug.py against the REFERENCE'S OWN transform classes
 (lib/datasets/tools/cv2_aug_transforms.py, cv2 stubbed -- it is not installed) under the same `random.seed`: resized size,
 crop origin and size, flip and brightness shift of every sample must be identical, i.e. Python's `random` stream is
-consumed in the reference's order. Runs where /root/reference exists. The collate pads follow collate.py:108-121."""
+consumed in the reference's order. The reference's decisions are a stored fixture (tests/golden/aug_decisions.json, written by
+oracle/make_golden.py). The collate pads follow collate.py:108-121."""
+import json
+import os
 import random
-import sys
-import types
 
 import numpy as np
 import pytest
-
-from oracle import ref_shim
 
 TRANS = {"trans_seq": ["random_resize", "random_crop", "random_hflip", "random_brightness"],
          "random_brightness": {"ratio": 0.7, "shift_value": 10},
          "random_hflip": {"ratio": 0.5, "swap_pair": []},
          "random_resize": {"ratio": 0.9, "method": "random", "scale_range": [0.5, 2.0], "aspect_range": [0.9, 1.1]},
          "random_crop": {"ratio": 1.0, "crop_size": [200, 120], "method": "random", "allow_outside_center": False}}
+AUG_SEED = 1234
+AUG_SIZES = [(256, 160), (200, 120), (333, 217), (150, 100), (512, 256)] * 6
 
 
 def _configer(cls):
@@ -29,43 +30,21 @@ def _configer(cls):
                       "std": [0.229, 0.224, 0.225]}})
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="reference tree not present")
-def test_decisions_match_reference_transform_classes():
-    ref_shim.install()
-    cv2 = sys.modules["cv2"]
-    cv2.INTER_CUBIC, cv2.INTER_NEAREST = 2, 0
-    cv2.resize = lambda x, size, interpolation=None: np.full((size[1], size[0]) + x.shape[2:], 128, dtype=x.dtype)
-    cv2.flip = lambda x, code: x
-    import collections
-    import collections.abc
-    import importlib
-    if not hasattr(collections, "Iterable"):
-        collections.Iterable = collections.abc.Iterable      # the reference predates Python 3.10 (:519)
-    aug = importlib.import_module("lib.datasets.tools.cv2_aug_transforms")
-    from lib.utils.tools.configer import Configer as RefConfiger
-    log = []
-    orig = aug._BaseTransform._process
-
-    def spy(self, img, data_dict, skip, *args, **kw):
-        out_img, out = orig(self, img, data_dict, skip, *args, **kw)
-        log[-1].append((type(self).__name__, bool(skip), args, out_img.shape, int(out_img.reshape(-1)[0])))
-        return out_img, out
-    aug._BaseTransform._process = spy
-    try:
-        compose = aug.CV2AugCompose(_configer(RefConfiger), split="train")
-        sizes = [(256, 160), (200, 120), (333, 217), (150, 100), (512, 256)] * 6
-        random.seed(1234)
-        for (w, h) in sizes:
-            log.append([])
-            compose(np.full((h, w, 3), 128, np.uint8), labelmap=np.zeros((h, w), np.float32))
-    finally:
-        aug._BaseTransform._process = orig
+def test_decisions_match_reference_transform_classes(golden_dir):
+    """Against the decisions the reference's transform classes took under the same seed, stored by oracle/make_golden.py
+    (--only aug_decisions) in tests/golden/aug_decisions.json: per sample and transform [name, skipped, arguments, output
+    shape, first output value]."""
+    with open(os.path.join(golden_dir, "aug_decisions.json")) as f:
+        ref = json.load(f)
+    assert ref["seed"] == AUG_SEED and [tuple(s) for s in ref["sizes"]] == AUG_SIZES
+    log = ref["log"]
+    assert len(log) == len(AUG_SIZES)
     from contrastiveseg_amd.lib.datasets.tools.gpu_aug import GPUAugCompose
     from contrastiveseg_amd.lib.utils.tools.configer import Configer
     mine = GPUAugCompose(_configer(Configer), split="train")
-    random.seed(1234)
+    random.seed(AUG_SEED)
     n_flip = n_skip = 0
-    for (w, h), entries in zip(sizes, log):
+    for (w, h), entries in zip(AUG_SIZES, log):
         p = mine.draw(w, h)
         by = {e[0]: e for e in entries}
         _, skip, args, shape, _ = by["RandomResize"]
@@ -74,12 +53,12 @@ def test_decisions_match_reference_transform_classes():
         n_skip += skip
         _, skip, args, shape, _ = by["RandomCrop"]
         assert not skip and (args[0], args[1]) == (p.y_off, p.x_off) and tuple(args[2]) == (p.tw, p.th)
-        assert shape[:2] == (p.th, p.tw)
+        assert tuple(shape[:2]) == (p.th, p.tw)
         assert by["RandomHFlip"][1] == (not p.flip)
         n_flip += p.flip
         _, skip, _, _, value = by["RandomBrightness"]
         assert value - 128 == p.shift and (skip == (p.shift == 0) or not skip)
-    assert 0 < n_flip < len(sizes) and n_skip > 0          # both branches of the coins were exercised
+    assert 0 < n_flip < len(AUG_SIZES) and n_skip > 0          # both branches of the coins were exercised
 
 
 def test_collate_pads_and_unsupported_configs():

@@ -1,12 +1,13 @@
-"""Drop-in check of the model registry against the reference itself (build container only: skipped where
-/root/reference is absent): identical state_dict keys/shapes and, under the same torch seed, identical values --
-i.e. same construction order and initialisers -- so reference checkpoints interchange. CPU only, no forward."""
+"""Drop-in check of the model registry against the reference itself: identical state_dict keys/shapes and, under the same
+torch seed, identical values -- i.e. same construction order and initialisers -- so reference checkpoints interchange. The
+reference's side is a stored fixture (tests/golden/ref_state_digests.json, written by oracle/make_golden.py --only state_dicts):
+per model its number of entries, the SHA-256 of its [key, shape, dtype] list in order and the SHA-256 of all its values' bytes in
+order. CPU only, no forward."""
+import json
+import os
+
 import pytest
 import torch
-
-from oracle import ref_shim
-
-pytestmark = pytest.mark.skipif(not ref_shim.available(), reason="reference tree not present")
 
 CASES = [("hrnet_w48_contrast", "hrnet48", {}),
          ("hrnet_w48_ocr_contrast", "hrnet48", {}),
@@ -26,16 +27,33 @@ def _mine(model, backbone, contrast, num_classes=19):
     return ModelManager(cfg).semantic_segmentor()
 
 
+def state_layout(sd):
+    """[[key, shape, dtype], ...] of a state_dict, in its order."""
+    return [[k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in sd.items()]
+
+
+def state_digests(sd):
+    """(number of entries, SHA-256 of the layout, SHA-256 of every value's bytes in order): equal digests = same keys in the same
+    order, same shapes and dtypes, bit-identical values."""
+    import hashlib
+    values = hashlib.sha256()
+    for v in sd.values():
+        values.update(v.detach().contiguous().cpu().numpy().tobytes())
+    layout = hashlib.sha256(json.dumps(state_layout(sd), separators=(",", ":")).encode()).hexdigest()
+    return len(sd), layout, values.hexdigest()
+
+
+def reference_digests(golden_dir, model):
+    """{"entries", "layout_sha256", "values_sha256"} of the reference's model under torch.manual_seed(304)."""
+    with open(os.path.join(golden_dir, "ref_state_digests.json")) as f:
+        return json.load(f)[model]
+
+
 @pytest.mark.parametrize("model,backbone,contrast", CASES)
-def test_state_dict_identical_under_same_seed(model, backbone, contrast):
-    ref_shim.install()
-    from lib.models.model_manager import ModelManager as RefManager
-    cfg = ref_shim.configer(model_name=model, backbone=backbone, contrast=contrast)
+def test_state_dict_identical_under_same_seed(model, backbone, contrast, golden_dir):
+    ref = reference_digests(golden_dir, model)
     torch.manual_seed(304)
-    ref = RefManager(cfg).semantic_segmentor().state_dict()
-    torch.manual_seed(304)
-    mine = _mine(model, backbone, contrast).state_dict()
-    assert list(ref.keys()) == list(mine.keys())
-    for k in ref:
-        assert ref[k].shape == mine[k].shape, k
-        assert torch.equal(ref[k], mine[k]), k
+    n, layout, values = state_digests(_mine(model, backbone, contrast).state_dict())
+    assert n == ref["entries"]
+    assert layout == ref["layout_sha256"], "keys, their order, shapes or dtypes differ from the reference's"
+    assert values == ref["values_sha256"], "initial values differ from the reference's under the same seed"

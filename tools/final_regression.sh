@@ -6,4 +6,4 @@ done
 for w in cfg4 cfg5; do
   CSEG_BENCH_GUARD=0 timeout 600 python bench.py $S --workload $w 2>$O/$w.err | tail -1 > $O/$w.json; python -c "import json; d=json.loads(open('$O/$w.json').read()); print('$w:', d['ms_per_step'], 'ms/step', d['value'], 'img/s')"
 done
-CSEG_BENCH_GUARD=0 timeout 400 python bench.py $S 2>/dev/null | tail -1 > $O/cfg2_short.json; python -c "import json; d=json.loads(open('$O/cfg2_short.json').read()); print('cfg2 short:', d['ms_per_step'], d['roofline'].get('traffic'), d['roofline'].get('traffic_source'))"
+CSEG_BENCH_GUARD=0 timeout 400 python bench.py $S --full 2>/dev/null | tail -1 > $O/cfg2_short.json; python -c "import json; d=json.loads(open('$O/cfg2_short.json').read()); print('cfg2 short:', d['ms_per_step'], d['roofline'].get('traffic'), d['roofline'].get('traffic_source'))"

@@ -38,7 +38,7 @@ for step in "$@"; do
       grep -E "passed|failed|Error|Fatal|CSEG_ZZ|^FAILED" $O/tests.log | cut -c1-1500 | tail -12 ;;
     bench)
       a=${arg//,/ }; [ -z "$a" ] && a=$SHORT
-      CSEG_BENCH_GUARD=0 timeout 900 python bench.py $a > $O/bench.log 2> $O/bench.err; grep '^{"metric"' $O/bench.log | tail -1 | cut -c1-1800 | tee -a $O/bench_lines.txt
+      CSEG_BENCH_GUARD=0 timeout 900 python bench.py --full $a > $O/bench.log 2> $O/bench.err; grep '^{"metric"' $O/bench.log | tail -1 | cut -c1-1800 | tee -a $O/bench_lines.txt
       cp bench_detail.json $O/bench_detail.json 2>/dev/null ;;
     ab)
       for r in 1 2; do for on in 0 1; do
