@@ -15,6 +15,7 @@
 //   backward-data  dx[b][c][p] = sum_k wt[b][c][k] dy[b][k][p]
 //   weight grad.   dwt[b][c][k] = sum_p x[b][c][p] dy[b][k][p]      (the host folds the mask and the batch sum: tiny tensors)
 // All sums in a fixed order (no atomics): deterministic.
+// More than 32 classes (up to 256): csrc/cls1x1_wide.hip -- the same operators and weight layout as fp32 GEMMs on the matrix cores.
 #include "cseg_common.h"
 #include "cseg_hip.h"
 

@@ -2262,11 +2262,12 @@ class Cls1x1(Function):
         return dx, dwt, db, None
 
 
-def cls1x1_weights(weight, B, mask=None):
-    """[K, C, 1, 1] parameter -> wt [B, C, KP]: transposed, zero-padded to KP columns, times the channel mask [B, C] of a folded
-    Dropout2d (entries 0 or 1 / (1 - p)) when there is one. A few small tensor operations on 19 x 720 numbers, differentiable."""
+def cls1x1_weights(weight, B, mask=None, kp=None):
+    """[K, C, 1, 1] parameter -> wt [B, C, KP]: transposed, zero-padded to KP columns (`kp`; cls1x1_kp(K) by default), times the channel
+    mask [B, C] of a folded Dropout2d (entries 0 or 1 / (1 - p)) when there is one. A few small tensor operations on 19 x 720 numbers,
+    differentiable."""
     K_, C = weight.shape[:2]
-    KP = cls1x1_kp(K_)
+    KP = cls1x1_kp(K_) if kp is None else kp
     w2 = weight.reshape(K_, C).t()
     if KP > K_:
         w2 = torch.nn.functional.pad(w2, (0, KP - K_))
@@ -2277,6 +2278,71 @@ def cls1x1_weights(weight, B, mask=None):
 
 def cls1x1(x, weight, bias=None, mask=None):
     return Cls1x1.apply(x, cls1x1_weights(weight, x.shape[0], mask), bias, weight.shape[0])
+
+
+# 33 .. 256 classes (COCO-Stuff 171, ADE20K 150, Pascal-Context 60): csrc/cls1x1_wide.hip, the same three operators as exact-fp32 GEMMs
+# on the fp32-input matrix instruction (2 K flops per 4 bytes is compute-bound there: the streaming kernels above do not extend).
+# Opt-in (CSEG_CLS1X1_WIDE=1): measured faster than nn.Dropout2d + nn.Conv2d for the 720-channel heads behind a dropout (x 1.11 at 171
+# classes, x 1.30 at 150) but slower for the OCR classifier (512 channels, no dropout to fold: x 0.86) -- DESIGN.md section 14.3.
+CLS1X1_WIDE = os.environ.get("CSEG_CLS1X1_WIDE", "0") == "1"
+CLS1X1_WIDE_MAX_K = 256
+
+
+def cls1x1_wide_eligible(x, weight):
+    """NCHW fp32 on the GPU, a 1x1 kernel with 33 .. 256 output channels."""
+    return (CLS1X1_WIDE and _on_device(x) and x.dtype == F32 and weight.dtype == F32 and x.dim() == 4 and weight.dim() == 4
+            and tuple(weight.shape[2:]) == (1, 1) and CLS1X1_MAX_K < weight.shape[0] <= CLS1X1_WIDE_MAX_K
+            and weight.shape[1] == x.shape[1])
+
+
+def cls1x1_wide_kp(k):
+    """K padded to whole 32-class tiles of v_mfma_f32_32x32x2_f32: the one KP the cseg_cls1x1_wide_* entry points accept for this K."""
+    return (k + 31) // 32 * 32
+
+
+class Cls1x1Wide(Function):
+    """Cls1x1 for 33 .. 256 classes: same tensors, same saved tensors, same bias gradient; wt [B, C, cls1x1_wide_kp(K)]."""
+
+    @staticmethod
+    def forward(ctx, x, wt, bias, K_):
+        x, wt = x.contiguous(), wt.contiguous()
+        B, C, H, W = x.shape
+        KP = wt.shape[2]
+        y = torch.empty(B, K_, H, W, dtype=F32, device=x.device)
+        _hip.call("cseg_cls1x1_wide_fwd", _p(x, F32, "x"), _p(wt, F32, "wt"), _opt(bias, F32, "bias"), B, C, K_, KP, ctypes.c_long(H * W),
+                  _pf(y), _hip.stream_ptr())
+        ctx.save_for_backward(x, wt)
+        ctx.K = K_
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wt = ctx.saved_tensors
+        dy = dy.contiguous()
+        B, C, H, W = x.shape
+        K_, KP, P = ctx.K, wt.shape[2], H * W
+        dx = dwt = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            _hip.call("cseg_cls1x1_wide_bwd", _p(dy, F32, "dy"), _p(wt, F32, "wt"), B, C, K_, KP, ctypes.c_long(P), _pf(dx),
+                      _hip.stream_ptr())
+        if ctx.needs_input_grad[1]:
+            n = _hip.lib().cseg_cls1x1_wide_wrw_ws_floats(B, C, KP, ctypes.c_long(P))
+            if n == 0:
+                raise RuntimeError("cls1x1_wide_wrw: unsupported shape %s x %s" % (tuple(x.shape), tuple(dy.shape)))
+            ws = torch.empty(n, dtype=F32, device=x.device)
+            dwt = torch.empty(B, C, KP, dtype=F32, device=x.device)
+            _hip.call("cseg_cls1x1_wide_wrw", _p(x, F32, "x"), _p(dy, F32, "dy"), B, C, K_, KP, ctypes.c_long(P), _pf(ws), _pf(dwt),
+                      _hip.stream_ptr())
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = dy.sum((0, 2, 3))
+        return dx, dwt, db, None
+
+
+def cls1x1_wide(x, weight, bias=None, mask=None):
+    K_ = weight.shape[0]
+    return Cls1x1Wide.apply(x, cls1x1_weights(weight, x.shape[0], mask, cls1x1_wide_kp(K_)), bias, K_)
 
 
 # ----------------------------------------------------------------------------------------------------------

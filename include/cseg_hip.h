@@ -584,6 +584,22 @@ size_t cseg_cls1x1_wrw_ws_floats(int B, int C, int KP, long P);
 int cseg_cls1x1_wrw(const float* x, const float* dy, int B, int C, int K, int KP, long P, float* ws, float* dwt, cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The classifier convolution for 33 .. 256 classes (COCO-Stuff 171, ADE20K 150, Pascal-Context 60; csrc/cls1x1_wide.hip): the same
+ * three operators, tensors and per-image weight layout as cseg_cls1x1_* above (an addition to ABI 6: the four entry points above and
+ * their KP = 20 / 32 contract are unchanged), as exact-fp32 GEMMs on v_mfma_f32_32x32x2_f32 -- every result is a k-ordered fmaf chain,
+ * fixed summation order, no atomics. Any P >= 1 and C >= 1.
+ *   32 < K <= 256 and KP = K rounded up to a multiple of 32 (64 .. 256); anything else is refused (returns 0, cseg_last_error()).
+ *   wt / dwt [B][C][KP] with zero pad columns (dwt's pad columns are written as zeros); y / dy [B,K,P]: nothing beyond K is written.
+ *   ws: cseg_cls1x1_wide_wrw_ws_floats(B, C, KP, P) floats (0 = unsupported).
+ * ------------------------------------------------------------------------------------------------ */
+int cseg_cls1x1_wide_fwd(const float* x, const float* wt, const float* bias, int B, int C, int K, int KP, long P, float* y,
+                         cseg_stream_t stream);
+int cseg_cls1x1_wide_bwd(const float* dy, const float* wt, int B, int C, int K, int KP, long P, float* dx, cseg_stream_t stream);
+size_t cseg_cls1x1_wide_wrw_ws_floats(int B, int C, int KP, long P);
+int cseg_cls1x1_wide_wrw(const float* x, const float* dy, int B, int C, int K, int KP, long P, float* ws, float* dwt,
+                         cseg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * GPU data pipeline: random resize (cv2 INTER_CUBIC image / INTER_NEAREST label) -> random
  * crop -> horizontal flip -> brightness shift -> ToTensor + Normalize(div, mean, std) + label look-up + ReLabel(255,-1)
  * -> collate padding to the fixed input size, as ONE kernel over the output batch.  Replaces the per-sample CPU chain
