@@ -112,6 +112,12 @@ SIGNATURES = {
     "cseg_bn_group_bwd_reduce": (_c_int, [_ptr, _c_int, _c_int, _ptr, _ptr]),
     "cseg_bn_group_bwd_apply": (_c_int, [_ptr, _c_int, _c_int, _ptr, _ptr]),
     "cseg_conv3x3_split_dil_fwd": (_c_int, [_ptr, _ptr, _ptr, _ptr] + [_c_int] * 7 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
+    "cseg_conv3x3_split_dilany_plan": (_c_int, [_c_int, _c_int, ctypes.POINTER(_c_int), ctypes.POINTER(ctypes.c_long)]),
+    "cseg_conv3x3_split_dilany_packed_bytes": (ctypes.c_size_t, [_c_int] * 2),
+    "cseg_conv3x3_split_dilany_pack": (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr]),
+    "cseg_conv3x3_split_dilany_fwd": (_c_int, [_ptr, _ptr, _ptr, _ptr] + [_c_int] * 6 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
+    "cseg_conv3x3_split_dilany_wrw_ws_floats": (ctypes.c_size_t, [_c_int] * 6),
+    "cseg_conv3x3_split_dilany_wrw": (_c_int, [_ptr, _ptr] + [_c_int] * 6 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
     "cseg_conv3x3_s2_split_packed_bytes": (ctypes.c_size_t, [_c_int] * 2),
     "cseg_conv3x3_s2_split_plan": (_c_int, [_c_int] * 4 + [_ptr, _ptr]),
     "cseg_conv3x3_s2_split_pack": (_c_int, [_ptr] + [_c_int] * 4 + [_ptr, _ptr, _ptr]),

@@ -10,6 +10,7 @@
 #define CSEG_PACK_C3_16 1     // conv3x3_sb16.hip: 16-channel chunks, every K-step pairs two taps
 #define CSEG_PACK_C1 2        // conv1x1_sb.hip: 32 input channels per K-step
 #define CSEG_PACK_C3_S2T 3    // conv3x3_s2.hip: backward-data operator of the stride-2 convolution (taps grouped by output parity)
+#define CSEG_PACK_C3_ANY 4    // conv3x3_dilany.hip: nine tap slices of the conv1x1_sb.hip form (32 input channels per K-step)
 
 __host__ __device__ constexpr int pack_steps_c3(int Cin) { return (Cin / 32) * 9 + ((Cin & 31) ? 5 : 0); }
 __host__ __device__ constexpr int pack_steps_c3_16(int Cin) { return (Cin / 16) * 5; }
@@ -105,6 +106,33 @@ __device__ __forceinline__ void pack_elem_c1(const float* __restrict__ w, int Co
         v[j] = t;
     }
     pack_store<AR>(v, wscale, wp, (size_t)(co_tile * n_steps + ks) * NT + nt, lane);
+}
+
+// conv3x3_dilany.hip: tap-major, every tap a CSEG_PACK_C1 slice: Wp[co_tile][tap][kstep][nt][piece][lane],
+// value(co, ci = 32*kstep + 8g + j, tap), zero beyond the channel count. w = the forward's [Cout, Cin, 3, 3]; transpose_flip packs the
+// backward-data operator (maps Cout -> Cin channels, mirrored taps). One thread per (co_tile, tap, kstep, nt, lane).
+template <class AR>
+__device__ __forceinline__ void pack_elem_c3_any(const float* __restrict__ w, int Cout, int Cin, int transpose_flip, int NT, float wscale,
+                                                 uint4* __restrict__ wp, int e) {
+    const int conv_in = transpose_flip ? Cout : Cin;
+    const int n_steps = pack_steps_c1(conv_in);
+    int r = e;
+    const int lane = r & 63; r >>= 6;
+    const int nt = r % NT; r /= NT;
+    const int ks = r % n_steps; r /= n_steps;
+    const int tap = r % 9;
+    const int co_tile = r / 9;
+    const int g = lane >> 4, n = lane & 15;
+    const int oc = (co_tile * NT + nt) * 16 + n;           // output channel of THIS operator
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int ic = ks * 32 + 8 * g + j;                // input channel of THIS operator
+        float t = 0.f;
+        if (ic < conv_in) t = transpose_flip ? w[((size_t)ic * Cin + oc) * 9 + (8 - tap)] : w[((size_t)oc * Cin + ic) * 9 + tap];
+        v[j] = t;
+    }
+    pack_store<AR>(v, wscale, wp, (size_t)((co_tile * 9 + tap) * n_steps + ks) * NT + nt, lane);
 }
 
 // Backward-data operator of the 3x3 / stride 2 / pad 1 convolution (conv3x3_s2.hip): dx[ci][2 qy + py][2 qx + px] sums, over the

@@ -1091,7 +1091,7 @@ class SplitWeights(object):
             del self.table_cache[k]
 
     def get(self, weight, tag, flag, nt_req):
-        """-> (packed buffer uint8, max|w| record or None). tag: 'c3' | 'c1'."""
+        """-> (packed buffer uint8, max|w| record or None). tag: 'c3' | 'c3s2' | 'c3any' | 'c1'."""
         arith = split_arith_id()
         st = self.weights.get(id(weight))
         dkey = self._dkey(weight.device)
@@ -1131,6 +1131,10 @@ class SplitWeights(object):
                                                                                  ctypes.byref(kind), ctypes.byref(threads))
             nt = ctypes.c_int(int(nt_req))
             n_bytes = lib.cseg_conv3x3_s2_split_packed_bytes(conv_in, conv_out)
+        elif tag == "c3any":                             # any-rate dilated 3x3 (csrc/conv3x3_dilany.hip): f16x3, flag = backward-data operator
+            ok = arith == ARITH_IDS["f16x3"] and lib.cseg_conv3x3_split_dilany_plan(conv_in, conv_out, ctypes.byref(nt), ctypes.byref(threads))
+            kind = ctypes.c_int(4)
+            n_bytes = lib.cseg_conv3x3_split_dilany_packed_bytes(conv_in, conv_out)
         else:
             ok = lib.cseg_conv1x1_split_plan_arith(arith, conv_in, conv_out, ctypes.byref(nt), ctypes.byref(threads))
             kind = ctypes.c_int(2)
@@ -2016,7 +2020,12 @@ class Conv3x3DilSplit(Function):
         dx = conv3x3_dil_run(dy, weight, d, True, None, ax=ady) if ctx.needs_input_grad[0] else None
         dw = db = None
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] or want_db:
+        if CONV3X3_DIL_ANY and conv3x3_dilany_wrw_eligible(x, dy):
+            # (opt-in) the weight gradient on the tap-shifted split kernel instead of the library
+            dw = _on_wgrad_stream(lambda: conv3x3_dilany_wrw(x, dy, d, ax=ctx.ax, ady=ady), x, dy, ctx.ax, ady) \
+                if ctx.needs_input_grad[1] else None
+            db = bias_grad(dy) if want_db else None
+        elif ctx.needs_input_grad[1] or want_db:
             _, dw, db = torch.ops.aten.convolution_backward(
                 dy, x, weight, [weight.shape[0]] if ctx.has_bias else None, [1, 1], [d, d], [d, d], False, [0, 0], 1,
                 [False, bool(ctx.needs_input_grad[1]), bool(want_db)])
@@ -2025,6 +2034,111 @@ class Conv3x3DilSplit(Function):
 
 def conv3x3_dil_split(x, weight, bias, dil, want_stats=False):
     return Conv3x3DilSplit.apply(x, weight, bias, dil, want_stats)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# Dilated 3x3 convolutions at ANY rate (csrc/conv3x3_dilany.hip): nine tap-shifted 1x1 GEMMs in one launch, f16x3, all three
+# directions -- ASPP's rate-12/24/36 branches (reference lib/models/modules/decoder_block.py: im2col + rocBLAS forward, CK
+# backward-data and MIOpen weight gradient before) and, with the switch on, the weight gradients of the rate-2/4 layers above.
+# Opt-in (CSEG_CONV3X3_DIL_ANY=1): DESIGN.md section 15 has the rule the default follows and what was measured.
+# ----------------------------------------------------------------------------------------------------------
+CONV3X3_DIL_ANY = os.environ.get("CSEG_CONV3X3_DIL_ANY", "0") == "1"
+
+
+def conv3x3_dilany_eligible(x, weight, dilation):
+    """NCHW fp32 on the GPU, 3x3, square rate >= 1, channel counts the kernel tiles BOTH ways (multiples of 48 or 64: backward-data
+    swaps them), f16x3 arithmetic."""
+    if not (SPLIT_ARITH == "f16x3" and _on_device(x) and x.dtype == F32 and weight.dtype == F32 and x.dim() == 4
+            and x.is_contiguous() and weight.dim() == 4):
+        return False
+    co, ci, kh, kw = weight.shape
+    ok = lambda c: c % 48 == 0 or c % 64 == 0
+    dil = tuple(dilation)
+    return ((kh, kw) == (3, 3) and len(dil) == 2 and dil[0] == dil[1] and dil[0] >= 1 and ok(ci) and ok(co) and x.shape[1] == ci
+            and x.shape[2] * x.shape[3] < (1 << 30))
+
+
+def conv3x3_dilany_tiles(x, c_out):
+    nt16 = 256 if (c_out % 256 == 0 and c_out >= 512) else next(16 * nt for nt in (9, 8, 6, 4, 3) if c_out % (16 * nt) == 0)
+    return x.shape[0] * (c_out // nt16) * ((x.shape[2] * x.shape[3] + 255) // 256)
+
+
+def conv3x3_dilany_run(x, weight, dil, transpose_flip=False, bias=None, ax=None, addend=None, want_stats=False):
+    """y = conv2d(x, weight, bias, stride 1, padding dil, dilation dil) for any dil >= 1 (transpose_flip: the backward-data operator
+    applied to x); addend: a tensor of y's shape added in the epilogue (not together with want_stats)."""
+    if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise RuntimeError("conv3x3_dilany: needs a 4-d input and a [Cout, Cin, 3, 3] weight (got %s, %s)"
+                           % (tuple(x.shape), tuple(weight.shape)))
+    if SPLIT_ARITH != "f16x3":
+        raise RuntimeError("conv3x3_dilany: f16x3 arithmetic only (CSEG_SPLIT_ARITH=%s)" % SPLIT_ARITH)
+    co, ci = weight.shape[:2]
+    conv_in, conv_out = (co, ci) if transpose_flip else (ci, co)
+    B, cx, H, W = x.shape
+    if cx != conv_in or int(dil) < 1:
+        raise RuntimeError("conv3x3_dilany: input has %d channels, the operator takes %d (groups 1 only); dilation %d"
+                           % (cx, conv_in, int(dil)))
+    wp, aw = SPLIT_WEIGHTS.get(weight, "c3any", transpose_flip, 0)
+    if ax is None:
+        ax = tensor_amax(x)
+    y = torch.empty(B, conv_out, H, W, dtype=F32, device=x.device)
+    st = tile_stats_buffer(1, conv_out, B, H * W, 1, x.device) if (want_stats and CONV_EPILOGUE_STATS and addend is None) else None
+    _hip.call("cseg_conv3x3_split_dilany_fwd", _pq(x, "x"), wp.data_ptr(), _opt(bias, F32, "bias"),
+              _pq(addend, "addend") if addend is not None else _null(), B, conv_in, conv_out, H, W, int(dil),
+              _pf(ax), _pf(aw), _pf(y), _pf(st) if st is not None else _null(), _hip.stream_ptr())
+    return tile_stats_attach(y, st) if st is not None else y
+
+
+def conv3x3_dilany_wrw_eligible(x, dy):
+    return (SPLIT_ARITH == "f16x3" and _on_device(x) and x.dtype == F32 and dy.dtype == F32 and x.is_contiguous() and dy.is_contiguous()
+            and x.dim() == 4 and x.shape[1] % 16 == 0 and dy.shape[1] % 16 == 0 and x.shape[2] * x.shape[3] < (1 << 30))
+
+
+def conv3x3_dilany_wrw(x, dy, dil, ax=None, ady=None):
+    """dw [Cout,Cin,3,3] of the 3x3 / stride 1 / padding = dilation = dil convolution for the output gradient dy; deterministic."""
+    B, ci, H, W = x.shape
+    co = dy.shape[1]
+    if tuple(dy.shape) != (B, co, H, W):
+        raise RuntimeError("conv3x3_dilany_wrw: dy %s does not match x %s" % (tuple(dy.shape), tuple(x.shape)))
+    n = _hip.lib().cseg_conv3x3_split_dilany_wrw_ws_floats(B, ci, co, H, W, int(dil))
+    if n == 0 or SPLIT_ARITH != "f16x3":
+        raise RuntimeError("conv3x3_dilany_wrw: unsupported shape %s x %s at dilation %d (needs channels %% 16, f16x3)"
+                           % (tuple(x.shape), tuple(dy.shape), int(dil)))
+    ax = tensor_amax(x) if ax is None else ax
+    ady = tensor_amax(dy) if ady is None else ady
+    ws = torch.empty(n, dtype=F32, device=x.device)
+    dw = torch.empty(co, ci, 3, 3, dtype=F32, device=x.device)
+    _hip.call("cseg_conv3x3_split_dilany_wrw", _pq(x, "x"), _pq(dy, "dy"), B, ci, co, H, W, int(dil), _pf(ax), _pf(ady), _pf(ws),
+              _pf(dw), _hip.stream_ptr())
+    return dw
+
+
+class Conv3x3DilAny(Function):
+    """y = conv2d(x, weight, bias, stride 1, padding dil, dilation dil): forward, backward-data and weight gradient on the kernels of
+    csrc/conv3x3_dilany.hip, the bias gradient a plain reduction."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, dil, want_stats=False):
+        weight = weight.contiguous()
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias, ctx.dil = bias is not None, int(dil)
+        ctx.ax = amax_of(x)
+        return conv3x3_dilany_run(x, weight, dil, False, bias, ax=ctx.ax, want_stats=want_stats)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        d = ctx.dil
+        ady = amax_of(dy)
+        dy = dy.contiguous()
+        dx = conv3x3_dilany_run(dy, weight, d, True, None, ax=ady) if ctx.needs_input_grad[0] else None
+        dw = _on_wgrad_stream(lambda: conv3x3_dilany_wrw(x, dy, d, ax=ctx.ax, ady=ady), x, dy, ctx.ax, ady) \
+            if ctx.needs_input_grad[1] else None
+        db = bias_grad(dy) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        return dx, dw, db, None, None
+
+
+def conv3x3_dilany_split(x, weight, bias, dil, want_stats=False):
+    return Conv3x3DilAny.apply(x, weight, bias, dil, want_stats)
 
 
 def conv3x3_split_fork(x, weight, want_stats=False):

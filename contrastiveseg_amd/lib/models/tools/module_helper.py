@@ -177,7 +177,9 @@ class SplitConv2d(nn.Conv2d):
     padding and channel counts the split-operand kernels tile (multiples of 48 or 64 both ways), launches that fill the chip: forward
     and backward-data on cseg_conv1x1_split_* / cseg_conv3x3_split_* at ANY width (the 65 x 129 and 130 x 130 maps of these models are
     why the kernels lost their width % 4 requirement), weight gradients there too where kernels.conv*_wrw_wanted says so. Everything
-    else (dilated, strided, 7x7, class-count outputs) is the reference's convolution on MIOpen."""
+    else (strided, 7x7, class-count outputs, other dilated layers) is the reference's convolution on MIOpen. Dilated 3x3 layers with
+    padding = dilation: rate 2 / 4 on conv3x3_sb16d_kernel (kernels.conv3x3_dil_split); any other rate -- ASPP's 12 / 24 / 36 -- on the
+    tap-shifted kernels of csrc/conv3x3_dilany.hip when kernels.CONV3X3_DIL_ANY is on (opt-in), else on the libraries."""
 
     bn_follows = False        # see Conv3x3
 
@@ -199,6 +201,13 @@ class SplitConv2d(nn.Conv2d):
                 and K.conv3x3_sb_tiles(x, self.out_channels) >= K.CONV3X3_SB_MIN_TILES):
             # layer3 / layer4 of the dilated ResNets (rate 2 / 4): conv3x3_sb16d_kernel
             return K.conv3x3_dil_split(x, self.weight, self.bias, self.dilation[0], self.bn_follows)
+        elif (K.CONV3X3_DIL_ANY and K._on_device(x) and self.kernel_size == (3, 3) and self.stride == (1, 1)
+                and self.dilation[0] == self.dilation[1] and self.dilation != (1, 1) and self.padding == self.dilation
+                and self.groups == 1 and self.padding_mode == 'zeros' and x.dim() == 4
+                and K.conv3x3_dilany_eligible(x, self.weight, self.dilation)
+                and K.conv3x3_dilany_tiles(x, self.out_channels) >= K.CONV3X3_SB_MIN_TILES):
+            # (opt-in) any other rate -- ASPP's rate-12/24/36 branches: nine tap-shifted 1x1 GEMMs (csrc/conv3x3_dilany.hip)
+            return K.conv3x3_dilany_split(x, self.weight, self.bias, self.dilation[0], self.bn_follows)
         return super(SplitConv2d, self).forward(x)
 
 

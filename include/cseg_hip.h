@@ -398,6 +398,29 @@ int cseg_conv3x3_split_fwd_add(const float* x, const void* wp, const float* bias
 int cseg_conv3x3_split_dil_fwd(const float* x, const void* wp, const float* bias, const float* addend, int B, int Cin, int Cout, int H,
                                int W, int dil, int arith, const unsigned* amax_x, const unsigned* amax_w, float* y, float* stats,
                                cseg_stream_t stream);
+/* The same operator at ANY dilation d >= 1 (padding = d, stride 1, groups 1; additive, ABI 6; csrc/conv3x3_dilany.hip): the rate
+ * 12 / 24 / 36 branches of ASPP (reference lib/models/modules/decoder_block.py, 2048 -> 512 on 65 x 129 maps) and the weight gradients
+ * of the rate-2/4 layers. Nine tap-shifted 1x1 GEMMs accumulated in one launch over flat runs of 256 pixels; a source pixel's validity
+ * is decided from its row and column, so any width, any plane size, d >= H and d >= W are all regular. f16x3 only (amax_x / amax_w:
+ * CSEG_AMAX_WORDS records, required).
+ *   Channel contract in the direction being run: Cin % 16 == 0, Cout % 48 == 0 or % 64 == 0.
+ *   _plan: channel tiles per block + packing threads (kind CSEG_PACK_C3_ANY = 4 of cseg_split_pack_batch); 0 = outside the contract.
+ *   _pack: w = the forward's [Cout, Cin, 3, 3]; transpose_flip = 1 packs the backward-data operator (Cout -> Cin channels, taps
+ *     mirrored): conv_transpose2d(dy, w, stride 1, padding d, dilation d) = _fwd on that packing with Cin / Cout swapped.
+ *   _fwd: y = conv(x) + bias [+ addend] [+ BatchNorm statistics records [Cout][cseg_conv_stat_segments(1, B, H*W, 1)] as
+ *     cseg_conv1x1_split_fwd_st writes them]; bias / addend / stats nullable, addend and stats not together.
+ *   _wrw: dw [Cout, Cin, 3, 3]; Cin % 16 == 0, Cout % 16 == 0; ws: cseg_conv3x3_split_dilany_wrw_ws_floats(...) floats (per-split
+ *     partials, summed in a fixed order: two calls are bit-identical). */
+int cseg_conv3x3_split_dilany_plan(int conv_in, int conv_out, int* nt, long* threads);
+size_t cseg_conv3x3_split_dilany_packed_bytes(int Cin, int Cout);
+int cseg_conv3x3_split_dilany_pack(const float* w, int Cout, int Cin, int transpose_flip, const unsigned* amax_w, void* wp,
+                                   cseg_stream_t stream);
+int cseg_conv3x3_split_dilany_fwd(const float* x, const void* wp, const float* bias, const float* addend, int B, int Cin, int Cout,
+                                  int H, int W, int dil, const unsigned* amax_x, const unsigned* amax_w, float* y, float* stats,
+                                  cseg_stream_t stream);
+size_t cseg_conv3x3_split_dilany_wrw_ws_floats(int B, int Cin, int Cout, int H, int W, int dil);
+int cseg_conv3x3_split_dilany_wrw(const float* x, const float* dy, int B, int Cin, int Cout, int H, int W, int dil,
+                                  const unsigned* amax_x, const unsigned* amax_dy, float* ws, float* dw, cseg_stream_t stream);
 /* ws: cseg_conv3x3_sb_wrw_ws_floats(...) */
 int cseg_conv3x3_split_wrw(const float* x, const float* dy, int B, int Cin, int Cout, int H, int W, int arith,
                            const unsigned* amax_x, const unsigned* amax_dy, float* ws, float* dw, cseg_stream_t stream);
