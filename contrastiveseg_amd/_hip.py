@@ -134,6 +134,12 @@ SIGNATURES = {
     "cseg_cls1x1_wide_bwd": (_c_int, [_ptr, _ptr] + [_c_int] * 4 + [ctypes.c_long, _ptr, _ptr]),
     "cseg_cls1x1_wide_wrw_ws_floats": (ctypes.c_size_t, [_c_int, _c_int, _c_int, ctypes.c_long]),
     "cseg_cls1x1_wide_wrw": (_c_int, [_ptr, _ptr] + [_c_int] * 4 + [ctypes.c_long, _ptr, _ptr, _ptr]),
+    "cseg_ocr_gather_ws_floats": (ctypes.c_size_t, [_c_int] * 4 + [ctypes.c_long]),
+    "cseg_ocr_gather_fwd": (_c_int, [_ptr, _ptr, _c_float] + [_c_int] * 4 + [ctypes.c_long, _ptr, _ptr, _ptr, _ptr]),
+    "cseg_ocr_gather_bwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_float] + [_c_int] * 4 + [ctypes.c_long, _ptr, _ptr, _ptr]),
+    "cseg_ocr_attn_fwd": (_c_int, [_ptr, _ptr, _ptr, _c_float] + [_c_int] * 4 + [ctypes.c_long, _ptr, _ptr, _ptr]),
+    "cseg_ocr_attn_bwd_ws_floats": (ctypes.c_size_t, [_c_int] * 4 + [ctypes.c_long]),
+    "cseg_ocr_attn_bwd": (_c_int, [_ptr] * 5 + [_c_float] + [_c_int] * 4 + [ctypes.c_long] + [_ptr] * 5),
     "cseg_conv3x3_s2_wrw_ws_floats": (ctypes.c_size_t, [_c_int] * 5),
     "cseg_conv3x3_s2_split_wrw": (_c_int, [_ptr, _ptr] + [_c_int] * 6 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
     "cseg_conv1x1_split_packed_bytes": (ctypes.c_size_t, [_c_int, _c_int, _c_int]),

@@ -7,6 +7,7 @@ import os
 
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _hip
 
@@ -2457,6 +2458,115 @@ class Cls1x1Wide(Function):
 def cls1x1_wide(x, weight, bias=None, mask=None):
     K_ = weight.shape[0]
     return Cls1x1Wide.apply(x, cls1x1_weights(weight, x.shape[0], mask, cls1x1_wide_kp(K_)), bias, K_)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# The object-context block of the OCR models (csrc/ocr.hip): SpatialGather_Module and the attention of ObjectAttentionBlock2D with their
+# softmaxes fused into exact-fp32 GEMMs; the pixel x class map [B, K, H*W] is not written in the forward pass and not kept for the
+# backward pass. Opt-in (CSEG_OCR_FUSED=1); off = the torch composition of spatial_ocr_block.py.
+# ----------------------------------------------------------------------------------------------------------
+OCR_FUSED = os.environ.get("CSEG_OCR_FUSED", "0") == "1"
+OCR_MIN_K, OCR_MAX_K = 2, 256
+
+
+def ocr_kp(k):
+    """The one KP the cseg_ocr_* entry points accept for K classes: cls1x1_wide_kp(K), and two class tiles (64) up to 32 classes."""
+    return max(64, cls1x1_wide_kp(k))
+
+
+def ocr_fused_eligible(x, k, *others):
+    """`x` [B, C, H, W] and the per-image matrices `others` [B, C, K(, 1)] (or, for the gather, the scores [B, K, H, W]): fp32 on the
+    GPU, 2 .. 256 classes, one batch size."""
+    return (OCR_FUSED and x.dim() == 4 and OCR_MIN_K <= k <= OCR_MAX_K
+            and all(_on_device(t) and t.dtype == F32 and t.shape[0] == x.shape[0] for t in (x,) + others))
+
+
+class OcrGather(Function):
+    """ctx [B, C, K, 1] = softmax over the pixels of scale * probs [B, K, H, W], times feats [B, C, H, W]. Saved: the two inputs and the
+    2 B K row statistics of the softmax."""
+
+    @staticmethod
+    def forward(ctx, feats, probs, scale, grad_mode=True):
+        feats, probs = feats.contiguous(), probs.contiguous()
+        B, C, H, W = feats.shape
+        K_, P = probs.shape[1], H * W
+        KP = ocr_kp(K_)
+        n = _hip.lib().cseg_ocr_gather_ws_floats(B, C, K_, KP, ctypes.c_long(P))
+        if n == 0 or probs.numel() != B * K_ * P:
+            raise RuntimeError("ocr_gather_fwd: unsupported shape %s x %s" % (tuple(feats.shape), tuple(probs.shape)))
+        need = grad_mode and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        ws = torch.empty(n, dtype=F32, device=feats.device)
+        rstats = torch.empty(2, B, K_, dtype=F32, device=feats.device) if need else None
+        out = torch.empty(B, C, K_, 1, dtype=F32, device=feats.device)
+        _hip.call("cseg_ocr_gather_fwd", _p(probs, F32, "probs"), _p(feats, F32, "feats"), float(scale), B, C, K_, KP, ctypes.c_long(P),
+                  _pf(ws), _pf(rstats) if need else _null(), _pf(out), _hip.stream_ptr())
+        if need:
+            ctx.save_for_backward(feats, probs, rstats)
+        ctx.scale = float(scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dctx):
+        feats, probs, rstats = ctx.saved_tensors
+        dctx = dctx.contiguous()
+        B, C, H, W = feats.shape
+        K_, P = probs.shape[1], H * W
+        dfeats = torch.empty_like(feats) if ctx.needs_input_grad[0] else None
+        dprobs = torch.empty_like(probs) if ctx.needs_input_grad[1] else None
+        _hip.call("cseg_ocr_gather_bwd", _p(probs, F32, "probs"), _p(feats, F32, "feats"), _pf(rstats), _p(dctx, F32, "dctx"), ctx.scale,
+                  B, C, K_, ocr_kp(K_), ctypes.c_long(P), _pf(dprobs) if dprobs is not None else _null(),
+                  _pf(dfeats) if dfeats is not None else _null(), _hip.stream_ptr())
+        return dfeats, dprobs, None, None
+
+
+def ocr_gather(feats, probs, scale=1.0):
+    # (grad mode is off inside Function.forward: it is read here. Under torch.no_grad() no statistics are allocated or written)
+    return OcrGather.apply(feats, probs, scale, torch.is_grad_enabled())
+
+
+class OcrAttention(Function):
+    """out [B, C, H, W] = value [B, C, K] . softmax over the classes of scale * key^T [B, C, K] . q [B, C, H, W], NCHW in and out. Saved:
+    the three inputs and the 2 B H W per-pixel statistics of the softmax."""
+
+    @staticmethod
+    def forward(ctx, q, key, value, scale, grad_mode=True):
+        q, key, value = q.contiguous(), key.contiguous(), value.contiguous()
+        B, C, H, W = q.shape
+        K_, P = key.shape[2], H * W
+        KP = ocr_kp(K_)
+        if tuple(key.shape) != (B, C, K_) or tuple(value.shape) != (B, C, K_):
+            raise RuntimeError("ocr_attn_fwd: unsupported shape %s, %s, %s" % (tuple(q.shape), tuple(key.shape), tuple(value.shape)))
+        need = grad_mode and any(ctx.needs_input_grad[:3])
+        stats = torch.empty(B, 2, P, dtype=F32, device=q.device) if need else None
+        out = torch.empty(B, C, H, W, dtype=F32, device=q.device)
+        _hip.call("cseg_ocr_attn_fwd", _p(q, F32, "q"), _p(key, F32, "key"), _p(value, F32, "value"), float(scale), B, C, K_, KP,
+                  ctypes.c_long(P), _pf(out), _pf(stats) if need else _null(), _hip.stream_ptr())
+        if need:
+            ctx.save_for_backward(q, key, value, stats)
+        ctx.scale = float(scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        q, key, value, stats = ctx.saved_tensors
+        dout = dout.contiguous()
+        B, C, H, W = q.shape
+        K_, P = key.shape[2], H * W
+        KP = ocr_kp(K_)
+        n = _hip.lib().cseg_ocr_attn_bwd_ws_floats(B, C, K_, KP, ctypes.c_long(P))
+        if n == 0:
+            raise RuntimeError("ocr_attn_bwd: unsupported shape %s x %s" % (tuple(q.shape), tuple(key.shape)))
+        ws = torch.empty(n, dtype=F32, device=q.device)
+        dq, dkey, dvalue = torch.empty_like(q), torch.empty_like(key), torch.empty_like(value)
+        _hip.call("cseg_ocr_attn_bwd", _p(q, F32, "q"), _p(key, F32, "key"), _p(value, F32, "value"), _pf(stats), _p(dout, F32, "dout"),
+                  ctx.scale, B, C, K_, KP, ctypes.c_long(P), _pf(ws), _pf(dq), _pf(dkey), _pf(dvalue), _hip.stream_ptr())
+        return dq, dkey, dvalue, None, None
+
+
+def ocr_attention(q, key, value, scale):
+    return OcrAttention.apply(q, key, value, scale, torch.is_grad_enabled())
 
 
 # ----------------------------------------------------------------------------------------------------------

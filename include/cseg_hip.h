@@ -623,6 +623,30 @@ int cseg_cls1x1_wide_wrw(const float* x, const float* dy, int B, int C, int K, i
                          cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The object-context block of the OCR models (csrc/ocr.hip; an addition to ABI 6): soft region pooling and pixel -> region attention
+ * with their softmaxes fused into exact-fp32 GEMMs on v_mfma_f32_32x32x2_f32. Fixed summation order, no atomics, no host
+ * synchronisation. Any P >= 1 and C >= 1; 2 <= K <= 256 and KP = K rounded up to a multiple of 32, at least 64; anything else is
+ * refused (returns 0, cseg_last_error(); the size queries return 0). No tensor has pad columns in memory: nothing beyond K, C or P
+ * is written.
+ *   gather     s = softmax over P of scale * probs [B][K][P]; ctx [B][C][K] = sum_p s feats [B][C][P].
+ *              rstats [2][B][K] (row max, row sum of exp) is what the backward needs besides the inputs; NULL = kept in ws.
+ *              ws: cseg_ocr_gather_ws_floats floats. Backward: dprobs [B][K][P] and / or dfeats [B][C][P] (either may be NULL).
+ *   attention  a = softmax over K of scale * sum_c key [B][C][K] q [B][C][P]; out [B][C][P] = sum_k value [B][C][K] a.
+ *              stats [B][2][P] (per-pixel max, sum of exp) is written when not NULL. Backward: dq [B][C][P], dkey / dvalue [B][C][K];
+ *              ws: cseg_ocr_attn_bwd_ws_floats floats (a and the logit gradient, [B][K][P] each, and the split partial sums).
+ * ------------------------------------------------------------------------------------------------ */
+size_t cseg_ocr_gather_ws_floats(int B, int C, int K, int KP, long P);
+int cseg_ocr_gather_fwd(const float* probs, const float* feats, float scale, int B, int C, int K, int KP, long P, float* ws,
+                        float* rstats, float* ctx, cseg_stream_t stream);
+int cseg_ocr_gather_bwd(const float* probs, const float* feats, const float* rstats, const float* dctx, float scale, int B, int C,
+                        int K, int KP, long P, float* dprobs, float* dfeats, cseg_stream_t stream);
+int cseg_ocr_attn_fwd(const float* q, const float* key, const float* value, float scale, int B, int C, int K, int KP, long P,
+                      float* out, float* stats, cseg_stream_t stream);
+size_t cseg_ocr_attn_bwd_ws_floats(int B, int C, int K, int KP, long P);
+int cseg_ocr_attn_bwd(const float* q, const float* key, const float* value, const float* stats, const float* dout, float scale, int B,
+                      int C, int K, int KP, long P, float* ws, float* dq, float* dkey, float* dvalue, cseg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * GPU data pipeline: random resize (cv2 INTER_CUBIC image / INTER_NEAREST label) -> random
  * crop -> horizontal flip -> brightness shift -> ToTensor + Normalize(div, mean, std) + label look-up + ReLabel(255,-1)
  * -> collate padding to the fixed input size, as ONE kernel over the output batch.  Replaces the per-sample CPU chain
