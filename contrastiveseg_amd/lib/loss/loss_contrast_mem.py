@@ -73,7 +73,9 @@ class ContrastCELoss(nn.Module, ABC):
             loss_contrast = self.contrast_criterion(embedding, target, seg=seg, segment_queue=segment_queue,
                                                     pixel_queue=pixel_queue, seg_ready=preds.get('seg_ready'))
         else:
-            loss_contrast = 0
+            # no queues in `preds` (the validation pass: seg_net(..., is_eval=True) returns seg / embed only): the reference's
+            # `loss + 0 * 0` -- a zero scalar on the loss's device, made there without a host round trip
+            loss_contrast = loss.new_zeros(())
         # the two terms of the last call, detached (no host sync): the segmentation term is a smooth function of the weights, the
         # contrastive term is not (argmax decides hard / easy, rounding-level changes of the logits move anchors between the sets) --
         # tests that compare two implementations after an SGD step bound the former tightly and the latter loosely
@@ -106,7 +108,9 @@ class ContrastAuxCELoss(ContrastCELoss):
             loss_contrast = self.contrast_criterion(preds['embed'], target, seg=seg, segment_queue=segment_queue,
                                                     pixel_queue=pixel_queue, seg_ready=preds.get('seg_ready'))
         else:
-            loss_contrast = 0
+            # no queues in `preds` (the validation pass: seg_net(..., is_eval=True) returns seg / embed only): the reference's
+            # `loss + 0 * 0` -- a zero scalar on the loss's device, made there without a host round trip
+            loss_contrast = loss.new_zeros(())
         # the two terms of the last call, detached (no host sync): the segmentation term is a smooth function of the weights, the
         # contrastive term is not (argmax decides hard / easy, rounding-level changes of the logits move anchors between the sets) --
         # tests that compare two implementations after an SGD step bound the former tightly and the latter loosely
