@@ -152,6 +152,84 @@ def test_queue_update_matches_reference_golden(kw, monkeypatch):
     _replay(monkeypatch, "test_gpu_kernels", "test_trainer_enqueue_on_gpu_matches_reference_golden", kw, ("golden_dir",))
 
 
+# ---- mining, memory bank, contrastive term and upsample-CE at their edges (tests/loss_edge_cases.py), every parametrisation ----------
+def _edge(module, func):
+    cases = _cases(module, func)
+    wants_mp = "monkeypatch" in getattr(importlib.import_module(module), func).__code__.co_varnames
+
+    def decorate(body):
+        return pytest.mark.parametrize("kw", cases, ids=_ids(cases))(body)
+    return decorate, (lambda kw, monkeypatch: _replay(monkeypatch, module, func, dict(kw, monkeypatch=monkeypatch) if wants_mp else kw))
+
+
+_P, _R_PART = _edge("test_gpu_mining_edges", "test_classify_partition_edges")
+_G, _R_GATHER = _edge("test_gpu_mining_edges", "test_gather_anchors_equals_indexing")
+_S, _R_SCATTER = _edge("test_gpu_mining_edges", "test_scatter_anchor_grad_is_bit_exact")
+_QS, _R_QSUMS = _edge("test_gpu_queue_edges", "test_queue_count_and_class_sums")
+_QW, _R_QSEG = _edge("test_gpu_queue_edges", "test_queue_write_segments")
+_QP, _R_QPIX = _edge("test_gpu_queue_edges", "test_queue_write_pixels")
+_QE, _R_QENQ = _edge("test_gpu_queue_edges", "test_trainer_enqueue_at_171_classes_matches_oracle")
+_CC, _R_CON = _edge("test_gpu_loss_edges", "test_contrast_edges_match_float64_oracle")
+_CR, _R_CONREF = _edge("test_gpu_loss_edges", "test_contrast_refusals")
+_UC, _R_CE = _edge("test_gpu_loss_edges", "test_upsample_ce_edges_match_torch_float64_and_oracle")
+_UR, _R_CEREF = _edge("test_gpu_loss_edges", "test_upsample_ce_refuses_40_pixels_on_one_tap")
+
+
+@_P
+def test_classify_partition_edges(kw, monkeypatch):
+    _R_PART(kw, monkeypatch)
+
+
+@_G
+def test_gather_anchors_equals_indexing(kw, monkeypatch):
+    _R_GATHER(kw, monkeypatch)
+
+
+@_S
+def test_scatter_anchor_grad_is_bit_exact(kw, monkeypatch):
+    _R_SCATTER(kw, monkeypatch)
+
+
+@_QS
+def test_queue_count_and_class_sums(kw, monkeypatch):
+    _R_QSUMS(kw, monkeypatch)
+
+
+@_QW
+def test_queue_write_segments(kw, monkeypatch):
+    _R_QSEG(kw, monkeypatch)
+
+
+@_QP
+def test_queue_write_pixels(kw, monkeypatch):
+    _R_QPIX(kw, monkeypatch)
+
+
+@_QE
+def test_trainer_enqueue_at_171_classes_matches_oracle(kw, monkeypatch):
+    _R_QENQ(kw, monkeypatch)
+
+
+@_CC
+def test_contrast_edges_match_float64_oracle(kw, monkeypatch):
+    _R_CON(kw, monkeypatch)
+
+
+@_CR
+def test_contrast_refusals(kw, monkeypatch):
+    _R_CONREF(kw, monkeypatch)
+
+
+@_UC
+def test_upsample_ce_edges_match_torch_float64_and_oracle(kw, monkeypatch):
+    _R_CE(kw, monkeypatch)
+
+
+@_UR
+def test_upsample_ce_refuses_40_pixels_on_one_tap(kw, monkeypatch):
+    _R_CEREF(kw, monkeypatch)
+
+
 # ---- fused BatchNorm (+ residual, + ReLU), forward / backward / running statistics against torch fp64 ---------------------
 BN = _cases("test_gpu_bn", "test_fused_bn_matches_torch_fp64", lambda kw: kw["shape"][0] * kw["shape"][1] * kw["shape"][2] * kw["shape"][3] <= 1 << 20)
 
