@@ -569,6 +569,64 @@ def upsample_ce(seg, target, weight=None, ignore_index=-1, status=None):
 
 
 # ----------------------------------------------------------------------------------------------------------
+# test phase: multi-scale + flip fusion with the argmax, confusion matrix (csrc/ms_eval.hip)
+# ----------------------------------------------------------------------------------------------------------
+U8 = torch.uint8
+MS_MAX_TERMS = 8
+
+
+@torch.no_grad()
+def ms_fuse_argmax(terms, H, W, want_fused=False, want_pred=True):
+    """segmentor/tester.py:310-327, 380-398 + the argmax of :189 without any [B,K,H,W] tensor. `terms` is a list of
+    (plain, flipped or None, weight): plain = the net's coarse logits [B,K,h,w] at one scale, flipped = its output for the
+    horizontally mirrored input. -> pred u8 [B,H,W] (first index among equal maxima), or (pred, fused) with
+    fused = sum_i weight_i * (U(plain_i) + flip(U(flipped_i))) as fp32 [B,K,H,W] when want_fused (save_prob, tests);
+    pred is None when want_pred is False."""
+    n = len(terms)
+    if n < 1 or n > MS_MAX_TERMS:
+        raise RuntimeError("ms_fuse_argmax: %d terms (1 to %d are supported)" % (n, MS_MAX_TERMS))
+    B, K = terms[0][0].shape[:2]
+    keep, pa, pb = [], (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
+    hs, ws, wt = (ctypes.c_int * n)(), (ctypes.c_int * n)(), (ctypes.c_float * n)()
+    for i, (a, b, w) in enumerate(terms):
+        if a.dim() != 4 or a.shape[0] != B or a.shape[1] != K:
+            raise RuntimeError("ms_fuse_argmax: term %d is %s, expected [%d, %d, h, w]" % (i, tuple(a.shape), B, K))
+        a = a.contiguous()
+        pa[i] = _p(a, F32, "plain map").value
+        keep.append(a)
+        if b is not None:
+            if b.shape != a.shape:
+                raise RuntimeError("ms_fuse_argmax: the flipped map of term %d is %s, its plain map %s"
+                                   % (i, tuple(b.shape), tuple(a.shape)))
+            b = b.contiguous()
+            pb[i] = _p(b, F32, "flipped map").value
+            keep.append(b)
+        hs[i], ws[i], wt[i] = a.shape[2], a.shape[3], float(w)
+    dev = terms[0][0].device
+    pred = torch.empty(B, int(H), int(W), dtype=U8, device=dev) if want_pred else None
+    fused = torch.empty(B, K, int(H), int(W), dtype=F32, device=dev) if want_fused else None
+    _hip.call("cseg_ms_fuse_argmax", n, pa, pb, hs, ws, wt, B, K, int(H), int(W), _pf(pred) if want_pred else _null(),
+              _pf(fused) if want_fused else _null(), _hip.stream_ptr())
+    return (pred, fused) if want_fused else pred
+
+
+@torch.no_grad()
+def confusion_update(pred, target, confusion, ignore_index=-1):
+    """confusion [K,K] i64 (rows = ground truth, columns = prediction) += RunningScore._fast_hist(target, pred, K) with
+    target != ignore_index, in place on the device. pred u8, target i64, same number of elements."""
+    K = confusion.shape[0]
+    if confusion.dim() != 2 or confusion.shape[1] != K:
+        raise RuntimeError("confusion_update: the matrix is %s, expected [K, K]" % (tuple(confusion.shape),))
+    if pred.numel() != target.numel():
+        raise RuntimeError("confusion_update: %d predictions for %d targets" % (pred.numel(), target.numel()))
+    pred, target = pred.contiguous(), target.contiguous()
+    _hip.call("cseg_confusion_update", _p(pred, U8, "pred"), _p(target, I64, "target"), pred.numel(), K, int(ignore_index),
+              _p(confusion, I64, "confusion"), _hip.stream_ptr())
+    torch.autograd.graph.increment_version(confusion)      # written through a raw pointer
+    return confusion
+
+
+# ----------------------------------------------------------------------------------------------------------
 # memory bank
 # ----------------------------------------------------------------------------------------------------------
 @torch.no_grad()

@@ -186,6 +186,68 @@ class GPUAugLoader(object):
             yield {'img': out['img'], 'labelmap': out['labelmap']}
 
 
+class TestFolderLoader(object):
+    """Iterable of {'img': f32 [B,3,H,W], 'name': [stem], 'border_size': [(w, h)], 'pad_offset': [(left, up)] and, where label
+    files exist, 'labelmap': i64 [B,H,W] (-1 = ignore, the collate padding included)} for the test phase (the reference's
+    get_testloader, lib/datasets/data_loader.py:205-240, yields names and metas the same way). No shuffling, no dropped or
+    repeated samples: with a process group every rank takes its strided share, so that the reduced confusion matrix counts every
+    image once."""
+
+    def __init__(self, configer, image_dir, label_dir, batch_size, device, workers=8):
+        self.device = device
+        self.items = []
+        for name in sorted(os.listdir(image_dir)):
+            stem, ext = os.path.splitext(name)
+            if ext.lower() in IMG_EXT:
+                self.items.append((os.path.join(image_dir, name), stem))
+        if not self.items:
+            raise RuntimeError('no images under {}'.format(image_dir))
+        self.label_dir = label_dir if label_dir is not None and all(
+            os.path.exists(os.path.join(label_dir, stem + '.png')) for _, stem in self.items) else None
+        mode = configer.get('data', 'input_mode') if configer.exists('data', 'input_mode') else 'BGR'
+        self.bgr = (mode == 'BGR')
+        self.batch_size = max(1, int(batch_size))
+        self.transform = GPUBatchTransform(configer, 'test')
+        self.pool = ThreadPoolExecutor(max_workers=max(1, workers))
+
+    def _mine(self):
+        return self.items[get_rank()::get_world_size()]
+
+    def __len__(self):
+        return (len(self._mine()) + self.batch_size - 1) // self.batch_size
+
+    def _decode(self, item):
+        from PIL import Image
+        img = np.asarray(Image.open(item[0]).convert('RGB'))
+        if self.bgr:
+            img = img[:, :, ::-1]
+        lab = None
+        if self.label_dir is not None:
+            lab = np.asarray(Image.open(os.path.join(self.label_dir, item[1] + '.png')))
+            if lab.ndim == 3:
+                lab = lab[:, :, 0]
+            lab = np.ascontiguousarray(lab.astype(np.uint8))
+        return np.ascontiguousarray(img), lab
+
+    def __iter__(self):
+        mine = self._mine()
+        for i in range(0, len(mine), self.batch_size):
+            chunk = mine[i:i + self.batch_size]
+            items = list(self.pool.map(self._decode, chunk))
+            if len({it[0].shape for it in items}) != 1:
+                raise RuntimeError('images of one batch differ in size; the accelerated loader needs a common size')
+            ti = torch.from_numpy(np.stack([it[0] for it in items])).to(self.device)
+            tl = torch.from_numpy(np.stack([it[1] for it in items])).to(self.device) if self.label_dir is not None else None
+            out = self.transform(ti, tl)
+            params = out['aug_params']
+            batch = {'img': out['img'], 'name': [stem for _, stem in chunk],
+                     'border_size': [(int(p[4]), int(p[5])) for p in params.tolist()],
+                     'pad_offset': [(int(p[8]), int(p[9])) for p in params.tolist()]}
+            if tl is not None:
+                batch['labelmap'] = out['labelmap']
+            yield batch
+
+
 class DataLoader(object):
     def __init__(self, configer, device=None):
         self.configer = configer
@@ -205,3 +267,32 @@ class DataLoader(object):
         bs = max(1, self.configer.get('val', 'batch_size') // get_world_size())
         src = FolderSource(self.configer, dataset, bs, shuffle=False, drop_last=False, workers=self._workers())
         return GPUAugLoader(self.configer, src, self.device, 'val')
+
+    def get_testloader(self):
+        """Images of test.test_dir (default: <data_dir>/val/image) with their stems; labels from <image dir>/../label where every
+        image has one; resized / padded as test.data_transformer says (default: val.data_transformer, else the images' own size)."""
+        c = self.configer
+        image_dir = c.get('test', 'test_dir') if c.exists('test', 'test_dir') else None
+        if image_dir is None:
+            data_dir = c.get('data', 'data_dir')
+            image_dir = os.path.join(data_dir[0] if isinstance(data_dir, (list, tuple)) else data_dir, 'val', 'image')
+        if not os.path.isdir(image_dir):
+            raise RuntimeError('test image directory {} does not exist'.format(image_dir))
+        label_dir = os.path.join(os.path.dirname(os.path.normpath(image_dir)), 'label')
+        if not c.exists('test', 'data_transformer'):
+            if c.exists('val', 'data_transformer'):
+                c.add(['test', 'data_transformer'], dict(c.get('val', 'data_transformer')))
+            else:
+                from PIL import Image
+                first = sorted(n for n in os.listdir(image_dir) if os.path.splitext(n)[1].lower() in IMG_EXT)
+                if not first:
+                    raise RuntimeError('no images under {}'.format(image_dir))
+                with Image.open(os.path.join(image_dir, first[0])) as im:
+                    c.add(['test', 'data_transformer'], {'size_mode': 'fix_size', 'input_size': list(im.size),
+                                                         'align_method': 'only_pad', 'pad_mode': 'pad_right_down'})
+        bs = c.get('test', 'batch_size') if c.exists('test', 'batch_size') else \
+            (c.get('val', 'batch_size') if c.exists('val', 'batch_size') else 1)
+        bs = bs or 1
+        loader = TestFolderLoader(c, image_dir, label_dir if os.path.isdir(label_dir) else None, bs, self.device, self._workers())
+        Log.info('test: {} images under {}, labels: {}'.format(len(loader.items), image_dir, loader.label_dir is not None))
+        return loader

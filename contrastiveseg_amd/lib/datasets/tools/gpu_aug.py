@@ -40,6 +40,8 @@ class GPUAugCompose(object):
         self.split = split
         key = 'train_trans' if split == 'train' else 'val_trans'
         self.cfg = configer.get(key) if configer.exists(key) else {'trans_seq': []}
+        if split == 'test':
+            self.cfg = {'trans_seq': []}                   # the reference's test loader has no aug_transform (data_loader.py:205-240)
         if self.cfg.get('shuffle_trans_seq'):
             raise NotImplementedError('shuffle_trans_seq is outside the accelerated data path')
         self.seq = list(self.cfg.get('trans_seq', []))
@@ -114,7 +116,7 @@ class GPUBatchTransform(object):
     def __init__(self, configer, split='train'):
         self.configer = configer
         self.aug = GPUAugCompose(configer, split)
-        dt = configer.get('train' if split == 'train' else 'val', 'data_transformer')
+        dt = configer.get(split if split in ('train', 'test') else 'val', 'data_transformer')
         if dt.get('size_mode', 'fix_size') != 'fix_size':
             raise NotImplementedError("size_mode {!r}: only 'fix_size' is implemented".format(dt.get('size_mode')))
         if dt.get('align_method', 'only_pad') != 'only_pad':

@@ -35,6 +35,15 @@ class RunningScore(object):
         hist = self._fast_hist(label_trues.reshape(-1), label_preds.reshape(-1))
         self.confusion_matrix = hist if self.confusion_matrix is None else self.confusion_matrix + hist
 
+    def update_from_hist(self, hist):
+        """hist: int64 [K, K] counts (rows = ground truth, columns = prediction) accumulated elsewhere, e.g. by
+        kernels.confusion_update on the device; added to the running matrix."""
+        if tuple(hist.shape) != (self.n_classes, self.n_classes) or hist.dtype != torch.int64:
+            raise ValueError('update_from_hist: expected int64 [{0}, {0}], got {1} {2}'.format(self.n_classes, hist.dtype,
+                                                                                              tuple(hist.shape)))
+        self.reduced_confusion_matrix = None
+        self.confusion_matrix = hist.clone() if self.confusion_matrix is None else self.confusion_matrix + hist
+
     def reduce_scores(self):
         hist = self.confusion_matrix
         if hist is None:

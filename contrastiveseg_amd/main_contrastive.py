@@ -55,7 +55,8 @@ def build_parser():
                             ('--checkpoints_root', 'checkpoints:checkpoints_root', str),
                             ('--checkpoints_name', 'checkpoints:checkpoints_name', str),
                             ('--log_file', 'logging:log_file', str), ('--stdout_level', 'logging:stdout_level', str),
-                            ('--optim_method', 'optim:optim_method', str), ('--group_method', 'optim:group_method', str)]:
+                            ('--optim_method', 'optim:optim_method', str), ('--group_method', 'optim:group_method', str),
+                            ('--test_dir', 'test:test_dir', str), ('--out_dir', 'test:out_dir', str)]:
         p.add_argument(flag, default=None, type=typ, dest=dest)
     p.add_argument('REMAIN', nargs='*')
     return p
@@ -77,8 +78,12 @@ def main(argv=None):
     if args.cudnn:
         Log.warn('--cudnn true: MIOpen exhaustive find is ON (20+ min of warm-up on a fresh machine for HRNet-W48); the '
                  'default (off) uses immediate mode + the tuned records in contrastiveseg_amd/miopen_db')
+    if configer.get('phase') == 'test':
+        # ss_test / ms_test of the reference's TEST configs on the fused scoring kernel (segmentor/tester.py)
+        from contrastiveseg_amd.segmentor.tester import Tester
+        return Tester(configer).test()
     if configer.get('phase') != 'train':
-        Log.error('Phase: {} is outside the accelerated hot path (train only).'.format(configer.get('phase')))
+        Log.error('Phase: {} is outside the accelerated hot path (train and test only).'.format(configer.get('phase')))
         raise SystemExit(1)
     from contrastiveseg_amd.segmentor.trainer_contrastive import Trainer
     Trainer(configer).train()

@@ -1,0 +1,192 @@
+"""Test phase with the reference's surface (segmentor/tester.py:56-398: `Tester(configer).test()`, `ss_test`, `ms_test`) and
+config keys (test.mode, test.scale_search, optional test.scale_weights, test.batch_size, test.out_dir, test.save_prob,
+network.resume).
+
+What the reference does per scale -- upsample two coarse logit maps to the input size, flip one, add, scale, accumulate into a
+[B,K,H,W] tensor (:310-327, :380-398), then move everything to the host for the argmax (:169-189) -- is linear up to the argmax.
+Here the model runs once per scale and once more on the mirrored input, only the coarse `seg` maps are kept, and one
+kernels.ms_fuse_argmax call per batch writes the prediction as one byte per pixel; the fused fp32 map exists only under
+test.save_prob. Scoring (where ground truth exists) is kernels.confusion_update into an on-device RunningScore.
+
+Outside the accelerated path, refused by name: sscrop_test, mscrop_test, ms_test_depth, crf_ss_test, the offset path, and every
+data_transformer for which the reference's final cv2.resize(..., INTER_CUBIC) to the original size (:180-181) would not be the
+identity (anything but size_mode fix_size + align_method only_pad, the pair the loader implements). The colour `vis/` output is
+not written."""
+import os
+import time
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from contrastiveseg_amd import kernels as K
+from contrastiveseg_amd.lib.metrics.running_score import RunningScore
+from contrastiveseg_amd.lib.utils.distributed import get_rank
+from contrastiveseg_amd.lib.utils.tools.logger import Logger as Log
+
+SUPPORTED_MODES = ('ss_test', 'ms_test')
+REFUSED_MODES = ('sscrop_test', 'mscrop_test', 'ms_test_depth', 'crf_ss_test')
+
+
+def check_config(configer):
+    """Everything that can be refused before a model is built. -> (mode, scales, weights or None)."""
+    if configer.exists('data', 'use_offset') and configer.get('data', 'use_offset'):
+        raise NotImplementedError('data.use_offset {!r}: the offset path (offset_test) is outside the accelerated test phase'
+                                  .format(configer.get('data', 'use_offset')))
+    mode = configer.get('test', 'mode') if configer.exists('test', 'mode') else 'ss_test'
+    if mode not in SUPPORTED_MODES:
+        if mode in REFUSED_MODES:
+            raise NotImplementedError('test.mode {!r} is outside the accelerated test phase; supported: {}'
+                                      .format(mode, SUPPORTED_MODES))
+        raise NotImplementedError('test.mode {!r} is not a test mode; supported: {}'.format(mode, SUPPORTED_MODES))
+    scales, weights = [1.0], None
+    if mode == 'ms_test':
+        scales = list(configer.get('test', 'scale_search')) if configer.exists('test', 'scale_search') else [1.0]
+        if configer.exists('test', 'scale_weights') and configer.get('test', 'scale_weights') is not None:
+            weights = list(configer.get('test', 'scale_weights'))
+            if len(weights) != len(scales):
+                raise ValueError('test.scale_weights has {} entries for the {} scales of test.scale_search'
+                                 .format(len(weights), len(scales)))
+        if not 1 <= len(scales) <= K.MS_MAX_TERMS:
+            raise ValueError('test.scale_search has {} scales; 1 to {} are supported'.format(len(scales), K.MS_MAX_TERMS))
+    if configer.exists('test', 'data_transformer'):
+        dt = configer.get('test', 'data_transformer')
+        if dt.get('size_mode', 'fix_size') != 'fix_size' or dt.get('align_method', 'only_pad') != 'only_pad':
+            raise NotImplementedError('test.data_transformer {}: only size_mode fix_size + align_method only_pad is implemented (the '
+                                      'final resize to the original size is the identity there; it is not approximated)'.format(dt))
+    return mode, scales, weights
+
+
+def dataset_id_lut(configer):
+    """uint8 [256]: train id -> dataset id, the inverse of the loader's label encoding (reference :189-197: reduce_zero_label
+    adds one, then label_list relabels; ids that label_list does not cover become 0)."""
+    ids = np.arange(256, dtype=np.int64)
+    if configer.exists('data', 'reduce_zero_label') and configer.get('data', 'reduce_zero_label'):
+        ids = (ids + 1) & 255
+    if configer.exists('data', 'label_list'):
+        label_list = configer.get('data', 'label_list')
+        out = np.zeros(256, dtype=np.int64)
+        for i in range(configer.get('data', 'num_classes')):
+            out[ids == i] = label_list[i]
+        ids = out
+    return ids.astype(np.uint8)
+
+
+def to_dataset_ids(pred, configer):
+    """pred: uint8 array of train ids -> uint8 array of dataset ids."""
+    return dataset_id_lut(configer)[np.asarray(pred, dtype=np.uint8)]
+
+
+class Tester(object):
+    def __init__(self, configer, seg_net=None, test_loader=None):
+        self.configer = configer
+        self.mode, self.scales, self.weights = check_config(configer)
+        from contrastiveseg_amd.lib.models.model_manager import ModelManager
+        from contrastiveseg_amd.segmentor.tools.module_runner import ModuleRunner
+        self.module_runner = ModuleRunner(configer)
+        self.device = self.module_runner.device()
+        if seg_net is None:
+            seg_net = ModelManager(configer).semantic_segmentor()
+            if configer.exists('network', 'channels_last') and configer.get('network', 'channels_last'):
+                seg_net = seg_net.to(memory_format=torch.channels_last)
+            if not (configer.exists('network', 'resume') and configer.get('network', 'resume')):
+                Log.warn('network.resume is not set: testing a randomly initialised model')
+            seg_net = self.module_runner.load_net(seg_net)
+        self.seg_net = seg_net
+        self.seg_net.eval()
+        self.save_dir = configer.get('test', 'out_dir') if configer.exists('test', 'out_dir') else None
+        self.save_prob = bool(configer.exists('test', 'save_prob') and configer.get('test', 'save_prob'))
+        self.test_loader = test_loader
+        self.running_score = RunningScore(configer, ignore_index=-1)
+        self.lut = dataset_id_lut(configer)
+        self.last_miou = None
+
+    # ------------------------------------------------------------------------------------------------------
+    def _coarse(self, x):
+        out = self.seg_net(x, is_eval=True)
+        if isinstance(out, dict):
+            out = out['seg']
+        elif isinstance(out, (list, tuple)):
+            out = out[-1]
+        return out
+
+    @staticmethod
+    def _scaled(inputs, scale):
+        h, w = inputs.shape[-2:]
+        return F.interpolate(inputs, size=(int(h * scale), int(w * scale)), mode='bilinear', align_corners=True)
+
+    @torch.no_grad()
+    def _fuse(self, terms, inputs, want_fused):
+        h, w = inputs.shape[-2:]
+        return K.ms_fuse_argmax(terms, h, w, want_fused=want_fused)
+
+    @torch.no_grad()
+    def ss_test(self, inputs, scale=1, want_fused=False):
+        """reference :310-327 + the argmax: -> pred u8 [B,H,W], or (pred, fused) when want_fused."""
+        self.seg_net.eval()
+        return self._fuse([(self._coarse(self._scaled(inputs, scale)), None, 1.0)], inputs, want_fused)
+
+    @torch.no_grad()
+    def ms_test(self, inputs, want_fused=False, flip=True):
+        """reference :380-398 + the argmax: one forward per scale and one more on the mirrored input; only the coarse maps are kept.
+        flip=False leaves the mirrored pass out (ms_test of one scale is then ss_test)."""
+        self.seg_net.eval()
+        mirrored = torch.flip(inputs, dims=[3]) if flip else None
+        terms = []
+        for i, scale in enumerate(self.scales):
+            a = self._coarse(self._scaled(inputs, scale))
+            b = self._coarse(self._scaled(mirrored, scale)) if flip else None
+            terms.append((a, b, 1.0 if self.weights is None else self.weights[i]))
+        return self._fuse(terms, inputs, want_fused)
+
+    # ------------------------------------------------------------------------------------------------------
+    def _loader(self):
+        if self.test_loader is None:
+            from contrastiveseg_amd.lib.datasets.data_loader import DataLoader
+            self.test_loader = DataLoader(self.configer, self.device).get_testloader()
+        return self.test_loader
+
+    @torch.no_grad()
+    def test(self, data_loader=None):
+        from PIL import Image
+        if not self.save_dir or self.save_dir == 'none':
+            raise RuntimeError('test.out_dir (--out_dir) is not set')
+        loader = self._loader() if data_loader is None else data_loader
+        label_dir = os.path.join(self.save_dir, 'label')
+        os.makedirs(label_dir, exist_ok=True)
+        if self.save_prob:
+            os.makedirs(os.path.join(self.save_dir, 'prob'), exist_ok=True)
+        Log.info('save dir {}'.format(self.save_dir))
+        self.running_score.reset()
+        K_cls = self.configer.get('data', 'num_classes')
+        confusion = torch.zeros(K_cls, K_cls, dtype=torch.int64, device=self.device)
+        start, n_img, scored = time.time(), 0, False
+        for batch in loader:
+            inputs = batch['img']
+            if inputs.device != self.device:
+                inputs = inputs.to(self.device, non_blocking=True)
+            out = self.ms_test(inputs, self.save_prob) if self.mode == 'ms_test' else self.ss_test(inputs, 1, self.save_prob)
+            pred, fused = out if self.save_prob else (out, None)
+            labels = batch.get('labelmap')
+            if labels is not None:
+                # pixels outside an image's unpadded region carry the ignore label (-1): the loader's padding
+                K.confusion_update(pred, labels.to(self.device), confusion, ignore_index=-1)
+                scored = True
+            pred_np = pred.cpu().numpy()
+            for k, name in enumerate(batch['name']):
+                bw, bh = batch['border_size'][k]
+                x0, y0 = batch['pad_offset'][k] if 'pad_offset' in batch else (0, 0)
+                n_img += 1
+                Image.fromarray(self.lut[pred_np[k, y0:y0 + bh, x0:x0 + bw]]).save(os.path.join(label_dir, '{}.png'.format(name)))
+                if self.save_prob:
+                    logits = fused[k, :, y0:y0 + bh, x0:x0 + bw].permute(1, 2, 0)
+                    np.save(os.path.join(self.save_dir, 'prob', '{}.npy'.format(name)), torch.softmax(logits, dim=-1).cpu().numpy())
+                Log.info('{:4d} label map generated'.format(n_img))
+        Log.info('Test Time {:.3f}s'.format(time.time() - start))
+        self.running_score.update_from_hist(confusion)
+        self.running_score.reduce_scores()
+        if scored or float(self.running_score.reduced_confusion_matrix.sum()) > 0:
+            self.last_miou = float(self.running_score.get_mean_iou())
+            if get_rank() == 0:
+                Log.info('Test mIoU {:.6f}\tPixel acc {:.6f}'.format(self.last_miou, float(self.running_score.get_pixel_acc())))
+        return self.last_miou

@@ -360,13 +360,26 @@ class Trainer(object):
         self.seg_net.eval()
         self.pixel_loss.eval()
         score = RunningScore(self.configer, ignore_index=-1)
+        # CSEG_VAL_FUSED=1 (opt-in): upsampling + argmax as one kernel that writes one byte per pixel, and the confusion matrix as a
+        # second one (csrc/ms_eval.hip) -- the label-resolution logits (319 MB per batch of 8 at 19 classes) never exist
+        fused = os.environ.get('CSEG_VAL_FUSED', '0') == '1'
+        hist = None
         for data_dict in (self.val_loader if data_loader is None else data_loader):
             (inputs, targets), batch_size = self.data_helper.prepare_data(data_dict)
             outputs = self.seg_net(*inputs, is_eval=True)
             self.val_losses.update(self.pixel_loss(outputs, targets).item(), batch_size)
+            if fused:
+                n = score.n_classes
+                if hist is None:
+                    hist = torch.zeros(n, n, dtype=torch.int64, device=targets.device)
+                pred = K.ms_fuse_argmax([(outputs['seg'], None, 1.0)], targets.shape[-2], targets.shape[-1])
+                K.confusion_update(pred, targets, hist, ignore_index=-1)
+                continue
             seg = nn.functional.interpolate(outputs['seg'], size=targets.shape[-2:], mode='bilinear',
                                             align_corners=True)
             score.update(seg.argmax(1), targets)
+        if hist is not None:
+            score.update_from_hist(hist)
         # every rank joins the all-reduce, whether or not its validation shard held a batch (a rank that skipped it would
         # leave the others waiting); "was anything validated" is then read off the REDUCED matrix, identically on all ranks
         score.reduce_scores()

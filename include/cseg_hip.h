@@ -663,6 +663,29 @@ int cseg_augment_batch(const uint8_t* img, const uint8_t* lab, const int16_t* lu
                        int Ws, int Ht, int Wt, float div_value, const float* mean3, const float* std3, float* out_img,
                        int64_t* out_lab, cseg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Test phase (csrc/ms_eval.hip).  Replaces the tensor work of segmentor/tester.py:310-327, 380-398 (ss_test / ms_test) with
+ * the argmax of :189, and lib/metrics/running_score.py:_fast_hist.  No full-resolution [B,K,H,W] tensor is needed.
+ *
+ * Fusion: n_terms terms (1..8), all arrays HOST arrays of n_terms entries, copied into the kernel's argument block:
+ *   plain[i]   [B,K,hs[i],ws[i]] f32 device pointer: the net's coarse logits at one scale
+ *   flipped[i] same shape, the net's output for the horizontally mirrored input, or NULL (`flipped` itself may be NULL)
+ *   weights[i] the scale's weight (1.0f for the unweighted ms_test and for ss_test)
+ * Per output pixel and class, in this order:  v = 0;  v = v + weights[i] * (U(plain[i])[y,x] + U(flipped[i])[y,W-1-x])
+ * where U is bilinear(align_corners=True) to H x W with torch's fp32 source index.  Sources may be smaller or larger than the
+ * output, or one pixel wide / high.
+ *   pred  [B,H,W] u8, first index among equal maxima, or NULL;  fused [B,K,H,W] f32 (the value v), or NULL; not both NULL.
+ * K <= 256.  Deterministic (no atomics).
+ *
+ * Confusion matrix: confusion [K,K] i64 (rows = ground truth, columns = prediction) += the counts of
+ *   (target[i], pred[i]) over i < N with 0 <= target[i] < K, pred[i] < K, target[i] != ignore_index.
+ * pred [N] u8, target [N] i64, N < 2^31 per call.  Integer atomics: exact and order-independent.
+ * ------------------------------------------------------------------------------------------------ */
+int cseg_ms_fuse_argmax(int n_terms, const float* const* plain, const float* const* flipped, const int* hs, const int* ws,
+                        const float* weights, int B, int K, int H, int W, uint8_t* pred, float* fused, cseg_stream_t stream);
+int cseg_confusion_update(const uint8_t* pred, const int64_t* target, long N, int K, int ignore_index, int64_t* confusion,
+                          cseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
