@@ -156,6 +156,12 @@ SIGNATURES = {
     "cseg_ms_fuse_argmax": (_c_int, [_c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int), ctypes.POINTER(_c_int),
                                      ctypes.POINTER(_c_float)] + [_c_int] * 4 + [_ptr, _ptr, _ptr]),
     "cseg_confusion_update": (_c_int, [_ptr, _ptr, ctypes.c_long, _c_int, _c_int, _ptr, _ptr]),
+    "cseg_rmi_pool_blocks": (_c_int, [_c_int] * 4),
+    "cseg_rmi_pool_fwd": (_c_int, [_ptr, _ptr] + [_c_int] * 10 + [_ptr] * 5),
+    "cseg_rmi_cov": (_c_int, [_ptr, _ptr] + [_c_int] * 4 + [_ptr, _ptr, _ptr]),
+    "cseg_rmi_solve": (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr]),
+    "cseg_rmi_finish": (_c_int, [_ptr, _c_int, _ptr, _c_int, _c_int, _c_float, _c_int, _c_float, _ptr, _ptr, _ptr]),
+    "cseg_rmi_bwd": (_c_int, [_ptr] * 9 + [_c_int] * 6 + [_c_float, _c_int, _c_float, _ptr, _ptr, _ptr]),
     "cseg_conv_stat_segments":(ctypes.c_size_t, [_c_int] * 4),
     "cseg_conv3x3_split_fwd_st": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 7 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
     "cseg_conv1x1_split_fwd_st": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 5 + [_ptr, _ptr, _ptr, _ptr, _ptr]),

@@ -569,9 +569,119 @@ def upsample_ce(seg, target, weight=None, ignore_index=-1, status=None):
 
 
 # ----------------------------------------------------------------------------------------------------------
-# test phase: multi-scale + flip fusion with the argmax, confusion matrix (csrc/ms_eval.hip)
+# segmentation term: upsample + region mutual information (csrc/rmi.hip)
 # ----------------------------------------------------------------------------------------------------------
 U8 = torch.uint8
+F64 = torch.float64
+
+
+def rmi_pooled_size(H, W):
+    """F.max_pool2d(kernel 3, stride 3, padding 1) of an H x W map."""
+    return (int(H) - 1) // 3 + 1, (int(W) - 1) // 3 + 1
+
+
+@torch.no_grad()
+def rmi_pool(seg, target, radius=3, pool_way=0, pool_size=3, pool_stride=3):
+    """seg [B,K,h,w] f32 (coarse logits), target [B,H,W] i64 -> p_pool f32, route u8, l_pool u8 (each [B,K,hp,wp]) and the
+    per-block partials f64 [nb, 2] of (BCE sum, valid pixels): the pooled maps of lib/loss/rmi_loss.py:315-340 applied to the
+    bilinear(align_corners=True) upsampling of seg, which is never built."""
+    if seg.dim() != 4 or target.dim() != 3 or target.shape[0] != seg.shape[0]:
+        raise RuntimeError("rmi_pool: seg %s / target %s, expected [B,K,h,w] / [B,H,W]" % (tuple(seg.shape), tuple(target.shape)))
+    seg, target = seg.contiguous(), target.contiguous()
+    B, K, h, w = seg.shape
+    _, H, W = target.shape
+    hp, wp = rmi_pooled_size(H, W)
+    dev = seg.device
+    nb = max(_hip.lib().cseg_rmi_pool_blocks(B, K, H, W), 1)
+    p_pool = torch.empty(B, K, hp, wp, dtype=F32, device=dev)
+    route = torch.empty(B, K, hp, wp, dtype=U8, device=dev)
+    l_pool = torch.empty(B, K, hp, wp, dtype=U8, device=dev)
+    partial = torch.empty(nb, 2, dtype=F64, device=dev)
+    _hip.call("cseg_rmi_pool_fwd", _p(seg, F32, "seg"), _p(target, I64, "target"), B, K, h, w, H, W, int(radius), int(pool_way),
+              int(pool_size), int(pool_stride), _pf(p_pool), _pf(route), _pf(l_pool), _pf(partial), _hip.stream_ptr())
+    return p_pool, route, l_pool, partial
+
+
+@torch.no_grad()
+def rmi_cov(p_pool, l_pool):
+    """-> cov f64 [B,K,3,9,9] (Cl, Cp, Clp of the nine shifted 3 x 3 views, centred; rmi_loss.py:357-379) and the views' means
+    f64 [B,K,2,9] (labels, probabilities)."""
+    if p_pool.dim() != 4 or p_pool.shape != l_pool.shape:
+        raise RuntimeError("rmi_cov: p_pool %s / l_pool %s, expected two [B,K,hp,wp] maps" % (tuple(p_pool.shape), tuple(l_pool.shape)))
+    p_pool, l_pool = p_pool.contiguous(), l_pool.contiguous()
+    B, K, hp, wp = p_pool.shape
+    cov = torch.empty(B, K, 3, 9, 9, dtype=F64, device=p_pool.device)
+    means = torch.empty(B, K, 2, 9, dtype=F64, device=p_pool.device)
+    _hip.call("cseg_rmi_cov", _p(p_pool, F32, "p_pool"), _p(l_pool, U8, "l_pool"), B, K, hp, wp, _pf(cov), _pf(means), _hip.stream_ptr())
+    return cov, means
+
+
+@torch.no_grad()
+def rmi_solve(cov):
+    """cov f64 [..., 3, 9, 9] -> rmi f64 [...] (rmi_loss.py:374-390 per (image, class)) and grads f64 [..., 2, 9, 9]:
+    d rmi / d Cp plus its transpose, and d rmi / d Clp."""
+    if cov.dim() < 3 or tuple(cov.shape[-3:]) != (3, 9, 9):
+        raise RuntimeError("rmi_solve: cov is %s, expected [..., 3, 9, 9]" % (tuple(cov.shape),))
+    cov = cov.contiguous()
+    lead = tuple(cov.shape[:-3])
+    n = 1
+    for s in lead:
+        n *= s
+    rmi = torch.empty(lead, dtype=F64, device=cov.device)
+    grads = torch.empty(lead + (2, 9, 9), dtype=F64, device=cov.device)
+    _hip.call("cseg_rmi_solve", _p(cov, F64, "cov"), n, _pf(rmi), _pf(grads), _hip.stream_ptr())
+    return rmi, grads
+
+
+class UpsampleRMI(Function):
+    """loss_weight * RMILoss.forward_sigmoid(F.interpolate(seg, target.shape, bilinear, align_corners=True), target) of the reference
+    (lib/loss/rmi_loss.py:283-402) without a [B,K,H,W] tensor. Saved for the backward: p_pool, route, l_pool (pooled resolution), the
+    views' means, the 9 x 9 gradient matrices and V. No host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, seg, target, lam, lambda_way, loss_weight):
+        seg, target = seg.contiguous(), target.contiguous()
+        B, K, h, w = seg.shape
+        p_pool, route, l_pool, partial = rmi_pool(seg, target)
+        cov, means = rmi_cov(p_pool, l_pool)
+        rmi, grads = rmi_solve(cov)
+        outd = torch.empty(4, dtype=F64, device=seg.device)
+        out = torch.empty(1, dtype=F32, device=seg.device)
+        _hip.call("cseg_rmi_finish", _pf(partial), partial.shape[0], _pf(rmi), B, K, float(lam), int(bool(lambda_way)), float(loss_weight),
+                  _pf(outd), _pf(out), _hip.stream_ptr())
+        ctx.save_for_backward(seg, target, p_pool, route, l_pool, means, grads, outd)
+        ctx.coef = (float(lam), int(bool(lambda_way)), float(loss_weight))
+        ctx.mark_non_differentiable(outd)
+        return out[0].clone(), outd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_outd):
+        seg, target, p_pool, route, l_pool, means, grads, outd = ctx.saved_tensors
+        B, K, h, w = seg.shape
+        _, H, W = target.shape
+        d_seg = torch.empty_like(seg)
+        g_pool = torch.empty_like(p_pool)
+        g = g.reshape(1).to(F32).contiguous()
+        lam, lambda_way, loss_weight = ctx.coef
+        _hip.call("cseg_rmi_bwd", _p(seg, F32, "seg"), _p(target, I64, "target"), _pf(p_pool), _pf(route), _pf(l_pool), _pf(means),
+                  _pf(grads), _pf(outd), _p(g, F32, "d_loss"), B, K, h, w, H, W, lam, lambda_way, loss_weight, _pf(g_pool), _pf(d_seg),
+                  _hip.stream_ptr())
+        return d_seg, None, None, None, None
+
+
+def rmi_loss(seg, target, lam=0.5, lambda_way=1, loss_weight=1.0, want_terms=False):
+    """The RMI segmentation term on coarse (or label-resolution) logits. With want_terms also the f64 [4] device tensor
+    {loss, bce, rmi_loss, V}. Works under torch.no_grad() (the validation pass calls the criterion that way)."""
+    if seg.dim() != 4 or target.dim() != 3 or target.shape[0] != seg.shape[0]:
+        raise RuntimeError("rmi_loss: seg %s / target %s, expected [B,K,h,w] / [B,H,W]" % (tuple(seg.shape), tuple(target.shape)))
+    loss, outd = UpsampleRMI.apply(seg, target, lam, lambda_way, loss_weight)
+    return (loss, outd) if want_terms else loss
+
+
+# ----------------------------------------------------------------------------------------------------------
+# test phase: multi-scale + flip fusion with the argmax, confusion matrix (csrc/ms_eval.hip)
+# ----------------------------------------------------------------------------------------------------------
 MS_MAX_TERMS = 8
 
 

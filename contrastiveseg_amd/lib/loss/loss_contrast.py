@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from contrastiveseg_amd import kernels as K
 from contrastiveseg_amd.lib.loss.anchor_sampling import plan_selection
-from contrastiveseg_amd.lib.loss.loss_helper import FSAuxCELoss, FSCELoss
+from contrastiveseg_amd.lib.loss.loss_helper import FSAuxCELoss, FSAuxRMILoss, FSCELoss, FSRMILoss
 from contrastiveseg_amd.lib.utils import distributed as D
 from contrastiveseg_amd.lib.utils.tools.logger import Logger as Log
 
@@ -226,9 +226,9 @@ class ContrastCELoss(nn.Module, ABC):
         Log.info('ignore_index: {}'.format(ignore_index))
         self.loss_weight = self.configer.get('contrast', 'loss_weight')
         self.use_rmi = self.configer.get('contrast', 'use_rmi')
-        if self.use_rmi:
-            raise NotImplementedError("contrast.use_rmi: the RMI criterion is outside the accelerated hot path")
-        self.seg_criterion = FSCELoss(configer=configer)
+        # use_rmi: the reference constructs FSAuxRMILoss here and unpacks the single logit tensor as a pair, which cannot run;
+        # this criterion has no auxiliary map, so it takes FSRMILoss
+        self.seg_criterion = FSRMILoss(configer=configer) if self.use_rmi else FSCELoss(configer=configer)
         self.contrast_criterion = PixelContrastLoss(configer=configer)
 
     def forward(self, preds, target, with_embed=False):
@@ -257,9 +257,7 @@ class ContrastAuxCELoss(nn.Module, ABC):
         Log.info('ignore_index: {}'.format(ignore_index))
         self.loss_weight = self.configer.get('contrast', 'loss_weight')
         self.use_rmi = self.configer.get('contrast', 'use_rmi')
-        if self.use_rmi:
-            raise NotImplementedError("contrast.use_rmi: the RMI criterion is outside the accelerated hot path")
-        self.seg_criterion = FSAuxCELoss(configer=configer)
+        self.seg_criterion = FSAuxRMILoss(configer=configer) if self.use_rmi else FSAuxCELoss(configer=configer)
         self.contrast_criterion = PixelContrastLoss(configer=configer)
 
     def forward(self, preds, target, with_embed=False):

@@ -686,6 +686,38 @@ int cseg_ms_fuse_argmax(int n_terms, const float* const* plain, const float* con
 int cseg_confusion_update(const uint8_t* pred, const int64_t* target, long N, int K, int ignore_index, int64_t* confusion,
                           cseg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Region mutual information segmentation term (csrc/rmi.hip).  Replaces lib/loss/rmi_loss.py:283-402 (RMILoss.forward_sigmoid ->
+ * rmi_lower_bound) applied to F.interpolate(seg, (H, W), bilinear, align_corners=True); no [B,K,H,W] tensor is needed.
+ * Only rmi_radius 3, rmi_pool_way 0 (max pooling), rmi_pool_size = rmi_pool_stride = 3 (every *_RMI.json of the reference); the pooled
+ * map is hp x wp = ((H-1)/3+1) x ((W-1)/3+1) and must be at least 3 x 3.  A label is valid when 0 <= label < K.  Deterministic.
+ *
+ *   cseg_rmi_pool_fwd  seg [B,K,h,w] f32, target [B,H,W] i64 -> p_pool [B,K,hp,wp] f32 (window maximum of sigmoid * valid + 1e-6),
+ *                      route [B,K,hp,wp] u8 (row-major slot 0..8 of the window that won; the first among equal maxima, never padding),
+ *                      l_pool [B,K,hp,wp] u8 (pooled one-hot labels), partial [2 * cseg_rmi_pool_blocks(B,K,H,W)] f64
+ *                      (per block: BCE sum, valid pixels).
+ *   cseg_rmi_cov       -> cov [B*K][3][81] f64: Cl, Cp, Clp (rows: label views, columns: probability views) of the nine shifted views,
+ *                      centred;  means [B*K][18] f64 (label views, probability views).
+ *   cseg_rmi_solve     cov [n][3][81] -> rmi [n] f64 = sum_i log(chol(Cl - Clp (Cp + 1e-3 I)^-1 Clp^T + 1e-3 I)_ii + 1e-8),
+ *                      grads [n][2][81] f64: d rmi / d Cp + its transpose, d rmi / d Clp.
+ *   cseg_rmi_finish    -> outd [4] f64 {loss, bce, rmi_loss, V}, out [1] f32 loss;  loss = loss_weight * (lam * bce + (1 - lam) *
+ *                      rmi_loss) when lambda_way, else loss_weight * (bce + lam * rmi_loss);  bce = sum / (V + 1),
+ *                      rmi_loss = sum_c mean_b rmi[b,c] / 9.
+ *   cseg_rmi_bwd       d_loss [1] f32 (device) -> g_pool [B,K,hp,wp] f32 (scratch: d loss / d p_pool), d_seg [B,K,h,w] f32.
+ * ------------------------------------------------------------------------------------------------ */
+int cseg_rmi_pool_blocks(int B, int K, int H, int W);
+int cseg_rmi_pool_fwd(const float* seg, const int64_t* target, int B, int K, int h, int w, int H, int W, int rmi_radius,
+                      int rmi_pool_way, int rmi_pool_size, int rmi_pool_stride, float* p_pool, uint8_t* route, uint8_t* l_pool,
+                      double* partial, cseg_stream_t stream);
+int cseg_rmi_cov(const float* p_pool, const uint8_t* l_pool, int B, int K, int hp, int wp, double* cov, double* means,
+                 cseg_stream_t stream);
+int cseg_rmi_solve(const double* cov, int n, double* rmi, double* grads, cseg_stream_t stream);
+int cseg_rmi_finish(const double* partial, int n_blocks, const double* rmi, int B, int K, float lam, int lambda_way,
+                    float loss_weight, double* outd, float* out, cseg_stream_t stream);
+int cseg_rmi_bwd(const float* seg, const int64_t* target, const float* p_pool, const uint8_t* route, const uint8_t* l_pool,
+                 const double* means, const double* grads, const double* outd, const float* d_loss, int B, int K, int h, int w,
+                 int H, int W, float lam, int lambda_way, float loss_weight, float* g_pool, float* d_seg, cseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
