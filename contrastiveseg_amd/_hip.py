@@ -55,6 +55,7 @@ SIGNATURES = {
     "cseg_abi_version": (_c_int, []),
     "cseg_last_error": (ctypes.c_char_p, []),
     "cseg_classify_partition": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 7 + [_ptr] * 7 + [_ptr]),
+    "cseg_classify_partition_prezeroed": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 7 + [_ptr] * 7 + [_ptr]),
     "cseg_gather_anchors": (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr]),
     "cseg_scatter_anchor_grad": (_c_int, [_ptr, _c_int, _ptr, _c_int, _c_int, _c_int, _c_float, _ptr, _ptr]),
     "cseg_contrast_ws_bytes": (ctypes.c_size_t, [_c_int, _c_int]),
@@ -64,6 +65,14 @@ SIGNATURES = {
     "cseg_contrast_fwd_fused": (_c_int, [ctypes.POINTER(ContrastDesc), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "cseg_contrast_bwd_parts": (_c_int, [_c_int, _c_int, _c_int]),
     "cseg_contrast_bwd": (_c_int, [ctypes.POINTER(ContrastDesc), _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "cseg_sampling_ws_ints": (ctypes.c_size_t, [_c_int] * 3),
+    "cseg_sample_anchors": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 5 + [_ptr] * 7 + [_ptr]),
+    "cseg_mt_draw": (_c_int, [_ptr, _ptr, _ptr, _c_int, _ptr]),
+    "cseg_gather_anchors_dn": (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr]),
+    "cseg_contrast_fwd_dn": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_float, _c_float, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "cseg_contrast_bwd_parts_cap": (_c_int, [_c_int, _c_int]),
+    "cseg_contrast_bwd_dn": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_float, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "cseg_scatter_anchor_grad_dn": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_float, _ptr, _ptr]),
     "cseg_upcat_fwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),
     "cseg_upcat_fwd_amax": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr, _ptr]),
     "cseg_upcat_bwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),

@@ -23,8 +23,11 @@ def lib():
                 h.cseg_host_randperm_prefixes.restype = ctypes.c_int
                 h.cseg_host_randperm_prefixes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                           ctypes.c_void_p]
+                for name in ("cseg_host_mt_export", "cseg_host_mt_import"):
+                    getattr(h, name).restype = ctypes.c_int
+                    getattr(h, name).argtypes = [ctypes.c_void_p]
                 _lib = h
-            except OSError:
+            except (OSError, AttributeError):
                 _lib = None
     return _lib
 
@@ -47,3 +50,31 @@ def randperm_prefixes(n_list, keep, flat=False):
     if flat:
         return out
     return np.split(out, np.cumsum(keep)[:-1]) if len(keep) else []
+
+
+MT_WORDS = 625     # 624 mt19937 state words + pos, the index of the next word to temper (624 = regenerate first)
+
+
+def _mt_lib(what):
+    h = lib()
+    if h is None:
+        raise RuntimeError("%s needs libcseg_host.so (csrc_host/build.py; switched off by CSEG_NO_HOST_LIB): the state of torch's "
+                           "CPU generator cannot be read or written without it, and contrast.device_sampling has no fallback" % what)
+    return h
+
+
+def mt_export():
+    """State of torch's default CPU generator as uint32 [625] (numpy): 624 state words, then pos."""
+    out = np.empty(MT_WORDS, dtype=np.uint32)
+    if _mt_lib("mt_export").cseg_host_mt_export(out.ctypes.data_as(ctypes.c_void_p)) != 1:
+        raise RuntimeError("cseg_host_mt_export failed")
+    return out
+
+
+def mt_import(words):
+    """Sets torch's default CPU generator to the state `words` (uint32 [625], the layout of mt_export)."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    if words.shape != (MT_WORDS,):
+        raise ValueError("mt_import: expected %d words, got %s" % (MT_WORDS, words.shape))
+    if _mt_lib("mt_import").cseg_host_mt_import(words.ctypes.data_as(ctypes.c_void_p)) != 1:
+        raise RuntimeError("cseg_host_mt_import failed (pos must be in [1, 624])")

@@ -628,7 +628,7 @@ int make_col(const cseg_contrast_desc* d, ColSrc* c) {
 
 inline int round32(int x) { return (x + 31) / 32 * 32; }
 
-inline int bwd_splits(int N, int M, int D) {
+__host__ __device__ inline int bwd_splits(int N, int M, int D) {
     const int nI = (N + 31) / 32, nDt = (D + BW_DT * 32 - 1) / (BW_DT * 32), nJ = (M + 31) / 32;
     int want = (768 + nI * nDt - 1) / (nI * nDt);      // ~3 blocks per CU
     int max_split = (nJ + 3) / 4;                       // at least one tile per wave
@@ -639,7 +639,316 @@ inline int bwd_splits(int N, int M, int D) {
     return s;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Device-N variants (anchor sampling on the device, csrc/sampling.hip): the number of anchors N = header[0] exists only in device
+// memory. Grids and buffers are sized for the capacity Ncap; every kernel reads N first, sets M = N and is the arithmetic of the
+// kernel above for that N, in the same order -- the column split of the backward included (bwd_splits on the device). Blocks, rows
+// and splits beyond N write zeros (parts, anchors) or nothing and return. Self mode, three-launch forward. The row stride of S is
+// round32(Ncap); columns are written up to round32(N) as cseg_contrast_fwd does. N is clamped to [0, Ncap], and the gather / scatter
+// treat a row whose position or pixel is outside the B*P pixels as padding: the planner never produces either, the checks bound what a
+// wrong header could make these kernels touch.
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int device_n(const int32_t* header, int Ncap) { return min(max(header[0], 0), Ncap); }
+
+__device__ __forceinline__ ColSrc self_col(const float* anchors, const int32_t* a_lab, int N, int D) {
+    ColSrc c;
+    c.mode = 0; c.M = N; c.D = D;
+    c.rows = anchors; c.labs = a_lab;
+    c.segq = nullptr; c.pixq = nullptr; c.ms = 0; c.packed = 0;
+    return c;
+}
+
+__global__ __launch_bounds__(256) void gather_dn_kernel(const float* __restrict__ embed, int B, int D, int P,
+                                                        const int32_t* __restrict__ part_idx, const int32_t* __restrict__ sel_pos,
+                                                        const int32_t* __restrict__ header, int Ncap, float* __restrict__ anchors,
+                                                        int32_t* __restrict__ sel_pix) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= Ncap) return;
+    const int pos = r < device_n(header, Ncap) ? sel_pos[r] : -1;
+    const bool ok = pos >= 0 && pos < B * P;
+    const int pix = ok ? part_idx[pos] : -1;
+    if (pix < 0 || pix >= P) {
+        if (lane == 0) sel_pix[r] = -1;
+        for (int d = lane; d < D; d += 64) anchors[(size_t)r * D + d] = 0.f;
+        return;
+    }
+    const int b = pos / P;
+    if (lane == 0) sel_pix[r] = b * P + pix;
+    const float* src = embed + (size_t)b * D * P + pix;
+    for (int d = lane; d < D; d += 64) anchors[(size_t)r * D + d] = src[(size_t)d * P];
+}
+
+// rows >= N are skipped: the store is not an accumulation, and sel_pix is -1 there
+__global__ __launch_bounds__(256) void scatter_dn_kernel(const float* __restrict__ parts, const int32_t* __restrict__ sel_pix,
+                                                         const int32_t* __restrict__ header, int Ncap, int B, int D, int P,
+                                                         float scale, float* __restrict__ d_embed) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int N = device_n(header, Ncap);
+    if (r >= N) return;
+    const int n_parts = bwd_splits(N, N, D);
+    const int bp = sel_pix[r];
+    if (bp < 0 || bp >= B * P) return;
+    const int b = bp / P, pix = bp - b * P;
+    float* dst = d_embed + (size_t)b * D * P + pix;
+    for (int d = lane; d < D; d += 64) {
+        float acc = 0.f;
+        for (int s = 0; s < n_parts; ++s) acc += parts[((size_t)s * Ncap + r) * D + d];
+        dst[(size_t)d * P] = acc * scale;
+    }
+}
+
+__global__ __launch_bounds__(256) void s_gemm_dn_kernel(const float* __restrict__ A, const int32_t* __restrict__ a_lab,
+                                                        const int32_t* __restrict__ header, int Ncap, int D, float inv_tau,
+                                                        float* __restrict__ S, int ldS, int nJb) {
+    __shared__ __attribute__((aligned(16))) float As[SG_T * SG_LD];
+    __shared__ __attribute__((aligned(16))) float Cs[SG_T * SG_LD];
+    const int N = device_n(header, Ncap);
+    const int I0 = (blockIdx.x / nJb) * SG_T, J0 = (blockIdx.x % nJb) * SG_T;
+    if (I0 >= N || J0 >= N) return;                  // (the grid of cseg_contrast_fwd has ceil(N / 64) row and column tiles)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wi = wave >> 1, wj = wave & 1;
+    const int h = lane >> 5, r32 = lane & 31;
+    const ColSrc col = self_col(A, a_lab, N, D);
+    const f32x16 acc = s_tile_64(A, N, col, I0, J0, As, Cs);
+    const int j = J0 + wj * 32 + r32;
+    if (j < (N + 31) / 32 * 32) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int ii = I0 + wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (ii < N) S[(size_t)ii * ldS + j] = acc[r] * inv_tau;
+        }
+    }
+}
+
+// row_pass_kernel for N = header[0], M = N (the same statements)
+__global__ __launch_bounds__(256) void row_pass_dn_kernel(const float* __restrict__ S, int ldS, const float* __restrict__ A,
+                                                          const int32_t* __restrict__ a_lab, const int32_t* __restrict__ header, int D,
+                                                          float coef, float* __restrict__ row_stats, float* __restrict__ row_loss) {
+    __shared__ float red[4];
+    const int N = device_n(header, gridDim.x);         // (the grid is Ncap blocks)
+    const int i = blockIdx.x, tid = threadIdx.x;
+    if (i >= N) return;
+    const ColSrc col = self_col(A, a_lab, N, D);
+    const int M = col.M;
+    const float* row = S + (size_t)i * ldS;
+    const int yi = a_lab[i];
+    float m = -INFINITY;
+    for (int j = tid; j < M; j += 256) {
+        const float s = row[j];
+        m = (s > m || s != s) ? s : m;  // NaN propagates like torch.max
+    }
+    m = block_max(m, red, tid);
+    float neg = 0.f, cnt = 0.f;
+    for (int j = tid; j < M; j += 256) {
+        const int yj = col.label(j);
+        if (yj != yi) neg += expf(row[j] - m);
+        else if (j != i) cnt += 1.f;
+    }
+    neg = block_sum(neg, red, tid);
+    cnt = block_sum(cnt, red, tid);
+    float slp = 0.f, rs = 0.f;
+    for (int j = tid; j < M; j += 256) {
+        if (j != i && col.label(j) == yi) {
+            const float L = row[j] - m;
+            const float den = expf(L) + neg;
+            slp += L - logf(den);
+            rs += 1.f / den;
+        }
+    }
+    slp = block_sum(slp, red, tid);
+    rs = block_sum(rs, red, tid);
+    if (tid == 0) {
+        row_loss[i] = -coef * (slp / cnt);             // 0/0 -> NaN exactly like the reference (no positives)
+        float4 st = make_float4(m, neg, coef / ((float)N * cnt), rs);
+        *reinterpret_cast<float4*>(row_stats + 4 * (size_t)i) = st;
+    }
+}
+
+// N = 0 (the step's status is set): loss = 0 / 0 = NaN, the visible signal
+__global__ __launch_bounds__(256) void mean_dn_kernel(const float* __restrict__ row_loss, const int32_t* __restrict__ header,
+                                                      int Ncap, float* __restrict__ loss) {
+    __shared__ float red[4];
+    const int N = device_n(header, Ncap);
+    float v = 0.f;
+    for (int i = threadIdx.x; i < N; i += 256) v += row_loss[i];
+    v = block_sum(v, red, threadIdx.x);
+    if (threadIdx.x == 0) loss[0] = v / (float)N;
+}
+
+// bwd_kernel<true> for N = header[0], M = N (the same statements; the split of the columns from bwd_splits on the device). `parts` is
+// [nsplit_cap][Ncap][D]: tiles beyond N, splits beyond nsplit(N) and rows N <= ii < Ncap are written as zeros.
+__global__ __launch_bounds__(256) void bwd_dn_kernel(const float* __restrict__ S, int ldS, const float* __restrict__ A,
+                                                     const int32_t* __restrict__ a_lab, const int32_t* __restrict__ header, int Ncap,
+                                                     int D, const float* __restrict__ row_stats, const float* __restrict__ d_loss,
+                                                     float inv_tau, int nDg, float* __restrict__ parts) {
+    __shared__ float red[32][BW_DT * 32 + 4];
+    __shared__ __attribute__((aligned(16))) float cstage[4][32 * 32];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int h = lane >> 5, r32 = lane & 31;
+    const int It = blockIdx.x / nDg, dg = blockIdx.x % nDg;
+    const int split = blockIdx.y;
+    const int I0 = It * 32, d0 = dg * (BW_DT * 32);
+    const int N = device_n(header, Ncap);
+    const int nsplit = N > 0 ? bwd_splits(N, N, D) : 0;
+    if (I0 >= N || split >= nsplit) {
+        for (int e = threadIdx.x; e < 32 * BW_DT * 32; e += 256) {
+            const int rr = e / (BW_DT * 32), cc = e - rr * (BW_DT * 32);
+            const int ii = I0 + rr, dd = d0 + cc;
+            if (ii < Ncap && dd < D) parts[((size_t)split * Ncap + ii) * D + dd] = 0.f;
+        }
+        return;
+    }
+    const int nJ = (N + 31) / 32, per_split = (nJ + nsplit - 1) / nsplit;
+    const ColSrc col = self_col(A, a_lab, N, D);
+    const int M = N;
+    const int i = I0 + r32;
+    const bool i_ok = i < N;
+    const float4 sti = i_ok ? *reinterpret_cast<const float4*>(row_stats + 4 * (size_t)i)
+                            : make_float4(0.f, 1.f, 0.f, 0.f);
+    const int yi = i_ok ? a_lab[i] : -0x7ffffffe;
+
+    f32x16 acc[BW_DT];
+#pragma unroll
+    for (int t = 0; t < BW_DT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+    const int jt_lo = split * per_split, jt_hi = min(nJ, jt_lo + per_split);
+    for (int jt = jt_lo + wave; jt < jt_hi; jt += 4) {
+        const int J0 = jt * 32;
+        float hv[16];
+        // B operand: the 32 contrast rows of this column tile are staged feature tile by feature tile in a wave-private
+        // LDS block with coalesced 16-byte loads (8 lanes per 128-byte row segment) instead of 16 strided scalar loads
+        // per feature tile; missing rows (padding columns, zero tail of the bank) are staged as zeros.
+        const float* srow[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) srow[u] = col.row(J0 + (lane >> 3) + 8 * u);
+        float* cw = cstage[wave];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int jb = J0 + 8 * q + 4 * h;  // this lane's 4 consecutive columns for registers 4q..4q+3
+            const float4 s4 = i_ok ? ld4(S + (size_t)i * ldS + jb) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
+            const float* rp[4];
+            int lb[4];
+            col.decode4(jb, rp, lb);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int j = jb + t;
+                const bool j_ok = j < M;
+                const int yj = lb[t];
+                const bool same = (yj == yi);
+                const bool pos = same && (j != i), neg = !same;
+                float g = grad_elem(sv[t], sti, pos, neg);
+                {
+                    const float4 stj = j_ok ? *reinterpret_cast<const float4*>(row_stats + 4 * (size_t)j)
+                                            : make_float4(0.f, 1.f, 0.f, 0.f);
+                    g += grad_elem(sv[t], stj, pos, neg);
+                }
+                // a missing row (padding column or the zero tail of the bank) contributes 0 whatever H is
+                hv[4 * q + t] = (i_ok && rp[t]) ? g : 0.f;
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < BW_DT; ++t) {
+            const int dbase = d0 + t * 32 + (lane & 7) * 4;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float4 v = (srow[u] && dbase < D) ? ld4(srow[u] + dbase) : make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4*>(cw + ((lane >> 3) + 8 * u) * 32 + (lane & 7) * 4) = v;
+            }
+            CSEG_WAVE_LOCKSTEP();
+            float bv[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) bv[r] = cw[(8 * (r >> 2) + 4 * h + (r & 3)) * 32 + r32];
+            CSEG_WAVE_LOCKSTEP();                      // the next feature tile's stores must not overtake these reads
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(hv[r], bv[r], acc[t], 0, 0, 0);
+        }
+    }
+    // acc[t] layout: col = d0 + t*32 + (lane&31), rows I0 + (r&3) + 8*(r>>2) + 4*h
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int t = 0; t < BW_DT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float* p = &red[(r & 3) + 8 * (r >> 2) + 4 * h][t * 32 + r32];
+                    *p = (w == 0) ? acc[t][r] : *p + acc[t][r];
+                }
+        }
+        __syncthreads();
+    }
+    const float scale = d_loss[0] * inv_tau;
+    for (int e = threadIdx.x; e < 32 * BW_DT * 32; e += 256) {
+        const int rr = e / (BW_DT * 32), cc = e - rr * (BW_DT * 32);
+        const int ii = I0 + rr, dd = d0 + cc;
+        if (ii < Ncap && dd < D) parts[((size_t)split * Ncap + ii) * D + dd] = ii < N ? red[rr][cc] * scale : 0.f;
+    }
+}
+
 }  // namespace
+
+extern "C" int cseg_gather_anchors_dn(const float* embed, int B, int D, int P, const int32_t* part_idx, const int32_t* sel_pos,
+                                      const int32_t* header, int Ncap, float* anchors, int32_t* sel_pix, cseg_stream_t stream_) {
+    CSEG_REQUIRE(Ncap > 0 && B > 0 && D > 0 && P > 0 && (size_t)B * P < ((size_t)1 << 31), "gather_anchors_dn: bad shape");
+    hipLaunchKernelGGL(gather_dn_kernel, dim3((Ncap + 3) / 4), dim3(256), 0, (hipStream_t)stream_, embed, B, D, P, part_idx, sel_pos,
+                       header, Ncap, anchors, sel_pix);
+    CSEG_CHECK_LAUNCH("gather_dn_kernel");
+    return 1;
+}
+
+extern "C" int cseg_contrast_bwd_parts_cap(int Ncap, int D) {
+    int cap = 1;
+    for (int n = 1; n <= Ncap; ++n) {
+        const int s = bwd_splits(n, n, D);
+        if (s > cap) cap = s;
+    }
+    return cap;
+}
+
+extern "C" int cseg_scatter_anchor_grad_dn(const float* d_anchor_parts, const int32_t* sel_pix, const int32_t* header, int Ncap, int B,
+                                           int D, int P, float scale, float* d_embed, cseg_stream_t stream_) {
+    CSEG_REQUIRE(Ncap > 0 && B > 0 && D > 0 && P > 0 && (size_t)B * P < ((size_t)1 << 31), "scatter_anchor_grad_dn: bad shape");
+    hipLaunchKernelGGL(scatter_dn_kernel, dim3((Ncap + 3) / 4), dim3(256), 0, (hipStream_t)stream_, d_anchor_parts, sel_pix, header,
+                       Ncap, B, D, P, scale, d_embed);
+    CSEG_CHECK_LAUNCH("scatter_dn_kernel");
+    return 1;
+}
+
+extern "C" int cseg_contrast_fwd_dn(const float* anchors, const int32_t* a_lab, const int32_t* header, int Ncap, int D,
+                                    float temperature, float base_temperature, float* S_ws, float* row_stats, float* row_loss,
+                                    float* loss, cseg_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    CSEG_REQUIRE(Ncap > 0 && D > 0, "contrast (device N): empty problem");
+    CSEG_REQUIRE(D % 8 == 0, "contrast: D=%d must be a multiple of 8", D);
+    CSEG_REQUIRE(temperature > 0.f && base_temperature > 0.f, "contrast: temperatures must be > 0");
+    const int ldS = round32(Ncap);
+    const int nb = (Ncap + SG_T - 1) / SG_T;
+    hipLaunchKernelGGL(s_gemm_dn_kernel, dim3(nb * nb), dim3(256), 0, stream, anchors, a_lab, header, Ncap, D, 1.0f / temperature, S_ws,
+                       ldS, nb);
+    CSEG_CHECK_LAUNCH("s_gemm_dn_kernel");
+    hipLaunchKernelGGL(row_pass_dn_kernel, dim3(Ncap), dim3(256), 0, stream, S_ws, ldS, anchors, a_lab, header, D,
+                       temperature / base_temperature, row_stats, row_loss);
+    CSEG_CHECK_LAUNCH("row_pass_dn_kernel");
+    hipLaunchKernelGGL(mean_dn_kernel, dim3(1), dim3(256), 0, stream, row_loss, header, Ncap, loss);
+    CSEG_CHECK_LAUNCH("mean_dn_kernel");
+    return 1;
+}
+
+extern "C" int cseg_contrast_bwd_dn(const float* anchors, const int32_t* a_lab, const int32_t* header, int Ncap, int D,
+                                    float temperature, const float* S_ws, const float* row_stats, const float* d_loss,
+                                    float* d_anchor_parts, cseg_stream_t stream_) {
+    CSEG_REQUIRE(Ncap > 0 && D > 0 && D % 8 == 0 && temperature > 0.f, "contrast backward (device N): bad shape or temperature");
+    const int nI = (Ncap + 31) / 32, nDt = (D + BW_DT * 32 - 1) / (BW_DT * 32);
+    dim3 grid(nI * nDt, cseg_contrast_bwd_parts_cap(Ncap, D));
+    hipLaunchKernelGGL(bwd_dn_kernel, grid, dim3(256), 0, (hipStream_t)stream_, S_ws, round32(Ncap), anchors, a_lab, header, Ncap, D,
+                       row_stats, d_loss, 1.0f / temperature, nDt, d_anchor_parts);
+    CSEG_CHECK_LAUNCH("bwd_dn_kernel");
+    return 1;
+}
 
 extern "C" size_t cseg_contrast_ws_bytes(int N, int M) { return (size_t)round32(N) * round32(M) * sizeof(float); }
 

@@ -210,6 +210,29 @@ extern "C" int cseg_classify_partition(const float* seg, const int64_t* pred_in,
     return 1;
 }
 
+// cseg_classify_partition without its two hipMemsetAsync calls: the CALLER hands in zero-filled counts and status (filled by a
+// kernel). For callers that capture the launches into a hipGraph (contrast.device_sampling).
+extern "C" int cseg_classify_partition_prezeroed(const float* seg, const int64_t* pred_in, const int64_t* target, int B, int K, int h,
+                                                 int w, int H, int W, int ignore_label, int32_t* lab, int32_t* pred, int16_t* key,
+                                                 int32_t* counts, int32_t* seg_off, int32_t* part_idx, int32_t* status,
+                                                 cseg_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    CSEG_REQUIRE(B > 0 && K > 0 && h > 0 && w > 0 && H > 0 && W > 0, "classify_partition: empty shape");
+    CSEG_REQUIRE(seg || pred_in, "classify_partition: need seg or pred_in");
+    CSEG_REQUIRE(K <= 16383, "classify_partition: K=%d does not fit the int16 key", K);
+    CSEG_REQUIRE((size_t)B * h * w < ((size_t)1 << 31), "classify_partition: B*h*w overflows int32 indices");
+    const int P = h * w;
+    const float scale_y = (float)H / (float)h, scale_x = (float)W / (float)w;
+    dim3 g1((P + CLS_THREADS - 1) / CLS_THREADS, B);
+    hipLaunchKernelGGL(classify_kernel, g1, dim3(CLS_THREADS), sizeof(int) * 2 * K, stream, seg, pred_in, target, K, h, w,
+                       H, W, scale_y, scale_x, ignore_label, lab, pred, key, counts, status);
+    CSEG_CHECK_LAUNCH("classify_kernel");
+    dim3 g2(K, B);
+    hipLaunchKernelGGL(partition_kernel, g2, dim3(PART_THREADS), 0, stream, key, counts, K, P, seg_off, part_idx);
+    CSEG_CHECK_LAUNCH("partition_kernel");
+    return 1;
+}
+
 extern "C" int cseg_gather_anchors(const float* embed, int B, int D, int P, const int32_t* part_idx,
                                    const int32_t* sel_pos, int N, float* anchors, int32_t* sel_pix,
                                    cseg_stream_t stream_) {

@@ -55,4 +55,41 @@ extern "C" int cseg_host_randperm_prefixes(const int64_t* n_list, const int64_t*
     }
 }
 
+// State of the default CPU generator's mt19937 as 625 words: the 624 state words, then `pos` = index of the next word to temper
+// (624 = "regenerate first"; in ATen's terms pos = 625 - left_: a freshly seeded engine has left_ = 1, after the first draw
+// left_ = 624 and next_ = 1). The device-side sampling path (csrc/sampling.hip) continues the stream from this state and hands it back.
+extern "C" int cseg_host_mt_export(uint32_t* out) {
+    try {
+        auto gen = at::get_generator_or_default<at::CPUGeneratorImpl>(c10::nullopt, at::detail::getDefaultCPUGenerator());
+        std::lock_guard<std::mutex> lock(gen->mutex_);
+        const at::mt19937_data_pod d = gen->engine().data();
+        if (!d.seeded_ || d.left_ < 1 || d.left_ > at::MERSENNE_STATE_N) return 0;
+        for (int i = 0; i < at::MERSENNE_STATE_N; ++i) out[i] = d.state_[i];
+        out[at::MERSENNE_STATE_N] = (uint32_t)(at::MERSENNE_STATE_N + 1 - d.left_);
+        return 1;
+    } catch (...) {
+        return 0;
+    }
+}
+
+extern "C" int cseg_host_mt_import(const uint32_t* in) {
+    try {
+        const uint32_t pos = in[at::MERSENNE_STATE_N];
+        if (pos < 1 || pos > (uint32_t)at::MERSENNE_STATE_N) return 0;
+        auto gen = at::get_generator_or_default<at::CPUGeneratorImpl>(c10::nullopt, at::detail::getDefaultCPUGenerator());
+        std::lock_guard<std::mutex> lock(gen->mutex_);
+        at::mt19937 eng = gen->engine();
+        at::mt19937_data_pod d = eng.data();
+        for (int i = 0; i < at::MERSENNE_STATE_N; ++i) d.state_[i] = in[i];
+        d.seeded_ = true;
+        d.left_ = at::MERSENNE_STATE_N + 1 - (int)pos;
+        d.next_ = pos == (uint32_t)at::MERSENNE_STATE_N ? 0 : pos;      // left_ == 1: the next draw regenerates and resets next_
+        eng.set_data(d);
+        gen->set_engine(eng);
+        return 1;
+    } catch (...) {
+        return 0;
+    }
+}
+
 extern "C" int cseg_host_abi_version(void) { return 1; }

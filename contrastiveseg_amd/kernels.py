@@ -51,9 +51,11 @@ def _pf(t):
 # ----------------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def classify_partition(target, ignore_label, seg=None, predict=None, num_classes=None, feat_hw=None,
-                       want_maps=False):
+                       want_maps=False, prezeroed=False):
     """lib/loss/loss_contrast.py:131-134 + :183 + the unique/nonzero bookkeeping of :35-64, on the device.
-    Returns dict(counts [B,K,2], seg_off [B,K,2], part_idx [B,P], status [4], lab/pred [B,P] if want_maps)."""
+    Returns dict(counts [B,K,2], seg_off [B,K,2], part_idx [B,P], status [4], lab/pred [B,P] if want_maps).
+    prezeroed: counts and status are zero-filled here by fill kernels and the library issues no hipMemsetAsync (the form whose
+    launches the device-sampling route lets callers capture into a hipGraph)."""
     B, H, W = target.shape
     target = target.contiguous()
     if seg is not None:
@@ -68,16 +70,16 @@ def classify_partition(target, ignore_label, seg=None, predict=None, num_classes
     P = h * w
     dev = target.device
     out = {
-        "counts": torch.empty(B, K, 2, dtype=I32, device=dev),
+        "counts": (torch.zeros if prezeroed else torch.empty)(B, K, 2, dtype=I32, device=dev),
         "seg_off": torch.empty(B, K, 2, dtype=I32, device=dev),
         "part_idx": torch.empty(B, P, dtype=I32, device=dev),
-        "status": torch.empty(4, dtype=I32, device=dev),
+        "status": (torch.zeros if prezeroed else torch.empty)(4, dtype=I32, device=dev),
         "key": torch.empty(B, P, dtype=I16, device=dev),
     }
     if want_maps:
         out["lab"] = torch.empty(B, P, dtype=I32, device=dev)
         out["pred"] = torch.empty(B, P, dtype=I32, device=dev)
-    _hip.call("cseg_classify_partition", seg_p, pred_p, _p(target, I64, "target"), B, K, h, w, H, W,
+    _hip.call("cseg_classify_partition_prezeroed" if prezeroed else "cseg_classify_partition", seg_p, pred_p, _p(target, I64, "target"), B, K, h, w, H, W,
               int(ignore_label),
               _p(out["lab"], I32, "lab") if want_maps else _null(),
               _p(out["pred"], I32, "pred") if want_maps else _null(),
@@ -330,6 +332,98 @@ class GatherAnchors(Function):
         _hip.call("cseg_scatter_anchor_grad", _p(g, F32, "d_anchors"), 1, _p(ctx.sel_pix, I32, "sel_pix"),
                   g.shape[0], D, h * w, 1.0, _p(d_embed, F32, "d_embed"), _hip.stream_ptr())
         return d_embed, None, None, None
+
+
+# ----------------------------------------------------------------------------------------------------------
+# anchor sampling on the device (contrast.device_sampling)
+# ----------------------------------------------------------------------------------------------------------
+# "1" / "0" overrides the config key contrast.device_sampling of the bank-free criteria; unset = the config decides (default off).
+DEVICE_SAMPLING = os.environ.get("CSEG_DEVICE_SAMPLING")
+SAMPLE_HEADER_INTS = 8          # header of cseg_sample_anchors: N, T, n_view, draws, status bits
+MT_WORDS = 625                  # mt19937 state on the device: 624 words + pos (csrc_host/rng_draws.cpp)
+
+
+@torch.no_grad()
+def sample_anchors(cp, max_samples, max_views, rng_state, sticky):
+    """lib/loss/anchor_sampling.plan_selection on the device, from the outputs `cp` of classify_partition: returns sel_pos [Ncap],
+    a_lab [Ncap] (rows >= N: -1) and header [8]. Advances `rng_state` (i32 [625]: the bits of the mt19937 words) by the draws of the
+    step and ORs the step's status bits into `sticky` (i32 [1]). No host value depends on the data."""
+    counts = cp["counts"]
+    B, K = counts.shape[:2]
+    P = cp["part_idx"].shape[1]
+    dev = counts.device
+    Ncap = int(max_samples)
+    sel_pos = torch.empty(Ncap, dtype=I32, device=dev)
+    a_lab = torch.empty(Ncap, dtype=I32, device=dev)
+    header = torch.empty(SAMPLE_HEADER_INTS, dtype=I32, device=dev)
+    draws = torch.empty(B * P, dtype=I32, device=dev)
+    ws = torch.empty(_hip.lib().cseg_sampling_ws_ints(B, K, Ncap), dtype=I32, device=dev)
+    _hip.call("cseg_sample_anchors", _p(counts, I32, "counts"), _p(cp["seg_off"], I32, "seg_off"), _p(cp["status"], I32, "status"),
+              B, K, P, Ncap, int(max_views), _p(rng_state, I32, "rng_state"), _pf(draws), _pf(ws), _pf(sel_pos), _pf(a_lab),
+              _pf(header), _p(sticky, I32, "sticky"), _hip.stream_ptr())
+    return sel_pos, a_lab, header
+
+
+@torch.no_grad()
+def mt_draw(rng_state, n):
+    """The next n outputs of the device generator (i32 [n]: the bits of the tempered 32-bit words); advances rng_state."""
+    header = torch.zeros(SAMPLE_HEADER_INTS, dtype=I32, device=rng_state.device)
+    header[3] = int(n)
+    draws = torch.empty(max(int(n), 1), dtype=I32, device=rng_state.device)
+    _hip.call("cseg_mt_draw", _p(rng_state, I32, "rng_state"), _pf(header), _pf(draws), draws.numel(), _hip.stream_ptr())
+    return draws[:int(n)]
+
+
+class PixelContrastDevice(Function):
+    """PixelContrast (self mode, three-launch forward) with the number of anchors N = header[0] in device memory only: every buffer and
+    grid is sized for Ncap = sel_pos.numel(), every kernel reads N itself. Returns the loss (NaN when N = 0) and sel_pix [Ncap]
+    (rows >= N: -1). With a SparseGradSlot the backward deposits [Ncap, D] rows whose padding rows are exactly zero, at
+    sel_pix.clamp_min(0): a duplicated index that adds an exact zero keeps index_add_ deterministic."""
+
+    @staticmethod
+    def forward(ctx, embed, part_idx, sel_pos, a_lab, header, temperature, base_temperature, slot=None):
+        if not embed.is_contiguous():
+            embed = embed.contiguous()
+        B, D = embed.shape[:2]
+        P = embed.shape[2] * embed.shape[3]
+        Ncap = sel_pos.numel()
+        dev = embed.device
+        lib = _hip.lib()
+        anchors = torch.empty(Ncap, D, dtype=F32, device=dev)
+        sel_pix = torch.empty(Ncap, dtype=I32, device=dev)
+        _hip.call("cseg_gather_anchors_dn", _p(embed, F32, "embed"), B, D, P, _p(part_idx, I32, "part_idx"), _p(sel_pos, I32, "sel_pos"),
+                  _p(header, I32, "header"), Ncap, _pf(anchors), _pf(sel_pix), _hip.stream_ptr())
+        S = torch.empty(lib.cseg_contrast_ws_bytes(Ncap, Ncap) // 4, dtype=F32, device=dev)
+        row_stats = torch.empty(Ncap, 4, dtype=F32, device=dev)
+        row_loss = torch.empty(Ncap, dtype=F32, device=dev)
+        loss = torch.empty(1, dtype=F32, device=dev)
+        _hip.call("cseg_contrast_fwd_dn", _pf(anchors), _p(a_lab, I32, "a_lab"), _p(header, I32, "header"), Ncap, D, float(temperature),
+                  float(base_temperature), _pf(S), _pf(row_stats), _pf(row_loss), _pf(loss), _hip.stream_ptr())
+        ctx.saved = (anchors, a_lab, header, S, row_stats, sel_pix)
+        ctx.temperature = float(temperature)
+        ctx.slot = slot
+        ctx.embed_shape = embed.shape
+        ctx.mark_non_differentiable(sel_pix)
+        return loss.reshape(()), sel_pix
+
+    @staticmethod
+    def backward(ctx, g, _g_sel):
+        B, D, h, w = ctx.embed_shape
+        anchors, a_lab, header, S, row_stats, sel_pix = ctx.saved
+        dev = sel_pix.device
+        Ncap = sel_pix.numel()
+        n_parts = _hip.lib().cseg_contrast_bwd_parts_cap(Ncap, D)
+        parts = torch.empty(n_parts, Ncap, D, dtype=F32, device=dev)
+        d_loss = g.reshape(1).to(F32).contiguous()
+        _hip.call("cseg_contrast_bwd_dn", _pf(anchors), _pf(a_lab), _pf(header), Ncap, D, ctx.temperature, _pf(S), _pf(row_stats),
+                  _p(d_loss, F32, "d_loss"), _pf(parts), _hip.stream_ptr())
+        if ctx.slot is not None:
+            rows = parts.sum(0) if n_parts > 1 else parts[0]
+            return (ctx.slot.deposit(rows, sel_pix.clamp_min(0), ctx.embed_shape),) + (None,) * 7
+        d_embed = torch.zeros(B, D, h, w, dtype=F32, device=dev)
+        _hip.call("cseg_scatter_anchor_grad_dn", _pf(parts), _pf(sel_pix), _pf(header), Ncap, B, D, h * w, 1.0, _pf(d_embed),
+                  _hip.stream_ptr())
+        return (d_embed,) + (None,) * 7
 
 
 # ----------------------------------------------------------------------------------------------------------

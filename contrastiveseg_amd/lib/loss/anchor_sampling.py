@@ -99,3 +99,25 @@ def plan_selection(counts, max_samples, max_views, draw_images=None):
     row_img = np.tile(seg_img, n_view)
     row_lab = np.tile(seg_cls, n_view)
     return SelectionPlan(T, n_view, seg_img, seg_cls, row_img, row_off, row_lab)
+
+
+# status bits of the device planner (csrc/sampling.hip, header[4] and the sticky word of the criterion)
+STATUS_BAD_LABELS, STATUS_NO_SEGMENT, STATUS_TOO_MANY_SEGMENTS, STATUS_KEEP_RULE = 1, 2, 4, 8
+
+
+def sampling_status_messages(bits, max_samples=None, max_views=None):
+    """The host path's error messages for the status bits that contrast.device_sampling collected on the device (a step whose status
+    is set has N = 0 anchors and a NaN contrastive term). Returns a list, empty for bits == 0."""
+    bits = int(bits)
+    out = []
+    if bits & STATUS_BAD_LABELS:
+        out.append("PixelContrastLoss: label values are neither ignore_label nor in [0, num_classes); "
+                   "the HIP mining kernel handles classes 0..K-1 only")
+    if bits & STATUS_NO_SEGMENT:
+        out.append("PixelContrastLoss: no (image, class) segment has more than max_views=%s pixels" % max_views)
+    if bits & STATUS_TOO_MANY_SEGMENTS:
+        out.append("anchor sampling: the qualifying (image, class) segments exceed max_samples=%s; the "
+                   "reference fails on the empty view axis too" % max_samples)
+    if bits & STATUS_KEEP_RULE:
+        out.append("this shoud be never touched! (anchor sampling: neither the hard nor the easy pixels of a segment reach n_view / 2)")
+    return out

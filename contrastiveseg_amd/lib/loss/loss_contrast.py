@@ -23,13 +23,19 @@ Data-parallel (one process per GPU, RCCL). Two modes, chosen by `contrast.cross_
     single-process loss on the concatenated global batch. The anchor budget of the global set is
     max_samples * world_size by default (`contrast.cross_rank_budget`: 'per_rank' | 'global').
 The memory-bank criterion (loss_contrast_mem.py) always contrasts a rank's own anchors against its own copy of the
-bank, as the reference does; `cross_rank` does not apply to it."""
+bank, as the reference does; `cross_rank` does not apply to it.
+
+`contrast.device_sampling` (opt-in, CSEG_DEVICE_SAMPLING=0|1 overrides): the keep rule and the torch.randperm
+replicas run on the device too (csrc/sampling.hip), from a device copy of the CPU generator's mt19937 state, and the gather / contrast /
+scatter kernels read the number of anchors from device memory. No device-to-host copy, no data-dependent host value, so the criterion
+can be captured in a hipGraph; same picks, loss and gradient as the host path under the same seed."""
 from abc import ABC
 
 import numpy as np
 import torch
 import torch.nn as nn
 
+from contrastiveseg_amd import _host
 from contrastiveseg_amd import kernels as K
 from contrastiveseg_amd.lib.loss.anchor_sampling import plan_selection
 from contrastiveseg_amd.lib.loss.loss_helper import FSAuxCELoss, FSAuxRMILoss, FSCELoss, FSRMILoss
@@ -62,6 +68,15 @@ def _counts_to_host(cp):
     return counts
 
 
+def device_sampling_wanted(configer):
+    """contrast.device_sampling (bool, default false), overridden by CSEG_DEVICE_SAMPLING=0|1."""
+    want = bool(configer.get('contrast', 'device_sampling')) if configer.exists('contrast', 'device_sampling') else False
+    env = getattr(K, "DEVICE_SAMPLING", None)      # (a stand-in for the kernels module, as the CPU port of the tests, has no switches)
+    if env in ("0", "1"):
+        want = env == "1"
+    return want
+
+
 def _grad_slot(embed):
     """kernels.SparseGradSlot the projection head attached to the embedding it produced (row-sparse backward, opt-in:
     lib/models/modules/projection.py), or None = the dense zero-filled gradient."""
@@ -69,6 +84,8 @@ def _grad_slot(embed):
 
 
 class PixelContrastLoss(nn.Module, ABC):
+    uses_memory_bank = False     # loss_contrast_mem.PixelContrastLoss: True
+
     def __init__(self, configer):
         super(PixelContrastLoss, self).__init__()
         self.configer = configer
@@ -98,6 +115,15 @@ class PixelContrastLoss(nn.Module, ABC):
         assert self.cross_rank_rng in ('local', 'global')
         self._side = None            # side HIP stream for mining (created lazily on the first GPU call)
         self.last_selection = None   # {'sel_pix': i32 [N] (b*P+pixel, view-major), 'plan': SelectionPlan}
+        self.device_sampling = device_sampling_wanted(configer)
+        if self.device_sampling and self.uses_memory_bank:
+            # follow-up: the enqueue draws of Trainer._dequeue_and_enqueue come from the same CPU generator stream; one stream split over
+            # two generators would silently leave the reference's index sequence
+            raise NotImplementedError("contrast.device_sampling is not available for the memory-bank criteria (their enqueue draws "
+                                      "share the CPU generator stream with the anchor sampling)")
+        # plain attributes, not buffers: state_dict keys stay those of the reference
+        self._rng_state = None       # i32 [625] on the device: mt19937 words + pos, imported from torch's CPU generator on first use
+        self.sampling_sticky = None  # i32 [1] on the device: OR of the status bits of every step (Trainer._display reads it)
 
     # -- mining ------------------------------------------------------------------------------------------
     def _mine(self, feats, labels, predict, seg, seg_ready=None, gather=False):
@@ -145,6 +171,61 @@ class PixelContrastLoss(nn.Module, ABC):
                                % self.max_views)
         return plan
 
+    # -- device-side sampling -----------------------------------------------------------------------------
+    def _rng_on(self, dev):
+        """The device generator, created on first use from the state of torch's default CPU generator."""
+        if self._rng_state is None or self._rng_state.device != dev:
+            words = _host.mt_export()                               # raises without libcseg_host.so: no silent fallback
+            self._rng_state = torch.from_numpy(words.view(np.int32).copy()).to(dev)
+            self.sampling_sticky = torch.zeros(1, dtype=torch.int32, device=dev)
+        return self._rng_state
+
+    def import_rng_from_torch(self):
+        """Takes the state of torch's default CPU generator again (e.g. after torch.manual_seed), into the existing device buffer."""
+        if self._rng_state is not None:
+            self._rng_state.copy_(torch.from_numpy(_host.mt_export().view(np.int32).copy()))
+
+    def export_rng_to_torch(self):
+        """Hands the generator stream back: writes the device state into torch's default CPU generator (synchronises). For tests
+        and for code that goes on drawing from the CPU generator."""
+        if self._rng_state is not None:
+            _host.mt_import(self._rng_state.cpu().numpy().view(np.uint32))
+
+    def _forward_device(self, feats, labels, predict, seg, seg_ready):
+        """Mining, selection, gather, contrast: all enqueued, nothing read back. Mining and planning keep the side-stream fork and
+        join of _mine when the model recorded `seg_ready`."""
+        B, Dm, h, w = feats.shape
+        dev = feats.device
+        rng = self._rng_on(dev)
+
+        def run():
+            if seg is not None:
+                cp = K.classify_partition(labels, self.ignore_label, seg=seg, prezeroed=True)
+            else:
+                cp = K.classify_partition(labels, self.ignore_label, predict=predict.contiguous(),
+                                          num_classes=self.configer.get('data', 'num_classes'), feat_hw=(h, w), prezeroed=True)
+            return cp, K.sample_anchors(cp, self.max_samples, self.max_views, rng, self.sampling_sticky)
+        if seg_ready is None or seg is None or not seg.is_cuda:
+            cp, (sel_pos, a_lab, header) = run()
+        else:
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=dev)
+            main = torch.cuda.current_stream(dev)
+            with torch.cuda.stream(self._side):
+                self._side.wait_event(seg_ready)
+                cp, (sel_pos, a_lab, header) = run()
+                done = torch.cuda.Event()
+                done.record(self._side)
+            for t in (cp["part_idx"], sel_pos, a_lab, header):
+                t.record_stream(main)
+            seg.record_stream(self._side)
+            labels.record_stream(self._side)
+            main.wait_event(done)
+        loss, sel_pix = K.PixelContrastDevice.apply(feats, cp["part_idx"], sel_pos, a_lab, header, self.temperature,
+                                                    self.base_temperature, _grad_slot(feats))
+        self.last_selection = {"sel_pix": sel_pix, "header": header, "plan": None}
+        return loss
+
     # -- forward -----------------------------------------------------------------------------------------
     def forward(self, feats, labels=None, predict=None, seg=None, seg_ready=None):
         """feats [B,D,h,w] (L2-normalised embeddings), labels [B,H,W] long, and either `predict` [B,h,w] long
@@ -155,6 +236,11 @@ class PixelContrastLoss(nn.Module, ABC):
         P = h * w
         world = D.get_world_size()
         cross = (world > 1 or D.exercise_single_rank()) and self.cross_rank
+        if self.device_sampling:
+            if cross:
+                raise NotImplementedError("contrast.device_sampling with contrast.cross_rank on more than one rank (or under "
+                                          "CSEG_DIST_SINGLE_RANK=1) is a follow-up: the cross-rank set needs the global plan on the host")
+            return self._forward_device(feats, labels, predict, seg, seg_ready)
         cp = self._mine(feats, labels, predict, seg, seg_ready, gather=cross)
         if cross:
             return self._forward_cross_rank(feats, cp, P, world)

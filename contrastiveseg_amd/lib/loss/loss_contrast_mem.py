@@ -20,6 +20,8 @@ from contrastiveseg_amd.lib.utils.tools.logger import Logger as Log
 
 
 class PixelContrastLoss(_SelfPixelContrastLoss):
+    uses_memory_bank = True      # contrast.device_sampling is refused (loss_contrast.py)
+
     def forward(self, feats, labels=None, predict=None, queue=None, seg=None, segment_queue=None,
                 pixel_queue=None, seg_ready=None):
         """Reference signature is (feats, labels, predict, queue) with queue = cat(segment, pixel) [K, 2*ms, D]

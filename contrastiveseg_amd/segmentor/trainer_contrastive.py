@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from contrastiveseg_amd import _host
 from contrastiveseg_amd import kernels as K
+from contrastiveseg_amd.lib.loss.anchor_sampling import sampling_status_messages
 from contrastiveseg_amd.lib.loss.loss_manager import LossManager
 from contrastiveseg_amd.lib.metrics.running_score import RunningScore
 from contrastiveseg_amd.lib.models.model_manager import ModelManager
@@ -308,6 +309,14 @@ class Trainer(object):
         bad = sum((m.status[1] for m in self.pixel_loss.modules() if hasattr(m, 'bad_label_count')),
                   torch.zeros((), dtype=torch.int32, device=self._last_loss.device))
         disp = torch.stack([self._last_loss.float(), bad.float()])
+        # contrast.device_sampling: the status bits the device planner collected since the criterion was built, one entry per bit (the
+        # all-reduce below adds), in the same host read as the loss
+        samplers = [m for m in self.pixel_loss.modules() if getattr(m, 'sampling_sticky', None) is not None]
+        if samplers:
+            sticky = samplers[0].sampling_sticky.to(disp.device)
+            for m in samplers[1:]:
+                sticky = sticky | m.sampling_sticky.to(disp.device)
+            disp = torch.cat([disp, ((sticky >> torch.arange(4, device=disp.device)) & 1).float()])
         if is_distributed() and get_world_size() > 1:
             import torch.distributed as dist
             dist.all_reduce(disp)               # every rank learns about bad labels on any rank
@@ -317,6 +326,11 @@ class Trainer(object):
             raise RuntimeError("%d label values were neither ce_ignore_index nor in [0, num_classes): the fused CE "
                                "kernel dropped them (nn.CrossEntropyLoss would have asserted); fix the label ids or "
                                "loss.params.ce_ignore_index" % int(disp[1]))
+        if samplers:
+            bits = sum(1 << i for i, v in enumerate(disp[2:6]) if v > 0)
+            msgs = sampling_status_messages(bits, samplers[0].max_samples, samplers[0].max_views)
+            if msgs:
+                raise RuntimeError("; ".join(msgs))
         self.train_losses.update(disp[0], self._last_batch)
         if not is_distributed() or get_rank() == 0:
             Log.info('Train Epoch: {0}\tTrain Iteration: {1}\t'

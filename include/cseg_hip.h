@@ -44,6 +44,12 @@ int cseg_classify_partition(const float* seg, const int64_t* pred_in, const int6
                             int ignore_label, int32_t* lab, int32_t* pred, int16_t* key, int32_t* counts,
                             int32_t* seg_off, int32_t* part_idx, int32_t* status, cseg_stream_t stream);
 
+/* The same without the two hipMemsetAsync calls: counts and status arrive ZERO-FILLED (by a kernel of the caller). For callers
+ * whose launches are captured into a hipGraph (contrast.device_sampling). */
+int cseg_classify_partition_prezeroed(const float* seg, const int64_t* pred_in, const int64_t* target, int B, int K, int h, int w,
+                                      int H, int W, int ignore_label, int32_t* lab, int32_t* pred, int16_t* key, int32_t* counts,
+                                      int32_t* seg_off, int32_t* part_idx, int32_t* status, cseg_stream_t stream);
+
 /* Gather of the mined pixels.  Replaces lib/loss/loss_contrast.py:141-142 (NHWC copy of all embeddings) and
  * :85-87 (fancy-index gather).  embed stays NCHW [B,D,P].
  *   sel_pos [N] i32: b*P + seg_off + rank (position inside part_idx), rows already in contrast order
@@ -111,6 +117,45 @@ int cseg_contrast_fwd_fused(const cseg_contrast_desc* d, float* fused_ws, float*
 int cseg_contrast_bwd_parts(int N, int M, int D);
 int cseg_contrast_bwd(const cseg_contrast_desc* d, const float* S_ws, const float* row_stats,
                       const float* d_loss, float* d_anchor_parts, cseg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Anchor sampling on the device (contrast.device_sampling).  Replaces the host half of the mining,
+ * lib/loss/loss_contrast.py:39-48 and :66-82 (qualifying classes, n_view, the keep rule, torch.randperm per class): nothing
+ * is copied to the host and no launch parameter depends on the data. Under the same seed the picks are the reference's.
+ *   counts, seg_off [B,K,2], mine_status [4]: outputs of cseg_classify_partition
+ *   rng_state [625] u32: mt19937 of torch's CPU generator, 624 state words + pos (index of the next word to temper, 624 =
+ *             regenerate first); advanced in place by the draws of the step
+ *   draws     [B*P] u32 workspace; ws [cseg_sampling_ws_ints(B, K, max_samples)] i32 workspace
+ *   sel_pos, a_lab [Ncap = max_samples] i32: view-major row r = v*T + a holds b*P + seg_off + pick (hard picks first, then easy
+ *             ones) and the class; rows >= N are -1
+ *   header    [8] i32: [0] N = T * n_view, [1] T, [2] n_view, [3] draws of the step, [4] status bits: 1 = labels outside [0,K)
+ *             (mine_status[0] != 0), 2 = T == 0, 4 = T > max_samples (n_view == 0), 8 = the keep rule fell through. With a
+ *             non-zero status N = 0 and rng_state is left untouched.
+ *   sticky    [1] i32: status is ORed into it
+ * cseg_mt_draw: the generator alone, header[3] draws into draws[cap].
+ * ------------------------------------------------------------------------------------------------ */
+size_t cseg_sampling_ws_ints(int B, int K, int Ncap);
+int cseg_sample_anchors(const int32_t* counts, const int32_t* seg_off, const int32_t* mine_status, int B, int K, int P,
+                        int max_samples, int max_views, uint32_t* rng_state, uint32_t* draws, int32_t* ws, int32_t* sel_pos,
+                        int32_t* a_lab, int32_t* header, int32_t* sticky, cseg_stream_t stream);
+int cseg_mt_draw(uint32_t* rng_state, const int32_t* header, uint32_t* draws, int cap, cseg_stream_t stream);
+
+/* Device-N variants of the gather, the contrastive term (self mode, three-launch forward) and the scatter: N = header[0] is read
+ * by every kernel, grids and buffers are sized for Ncap. Same arithmetic in the same order as the entry points above for that N
+ * (M = N), the column split of the backward included. anchors [Ncap,D] (rows >= N zero), sel_pix [Ncap] (rows >= N: -1),
+ * S_ws cseg_contrast_ws_bytes(Ncap, Ncap) bytes, row_stats [Ncap,4], row_loss [Ncap], loss [1] (N = 0: NaN),
+ * d_anchor_parts [cseg_contrast_bwd_parts_cap(Ncap, D), Ncap, D]: rows >= N and splits >= cseg_contrast_bwd_parts(N, N, D) are
+ * zero. The scatter skips rows >= N. N is clamped to [0, Ncap]; a row whose position or pixel lies outside the B*P pixels is
+ * treated as padding (the planner never produces one: a bound on what a wrong header could make the kernels touch). */
+int cseg_gather_anchors_dn(const float* embed, int B, int D, int P, const int32_t* part_idx, const int32_t* sel_pos,
+                           const int32_t* header, int Ncap, float* anchors, int32_t* sel_pix, cseg_stream_t stream);
+int cseg_contrast_fwd_dn(const float* anchors, const int32_t* a_lab, const int32_t* header, int Ncap, int D, float temperature,
+                         float base_temperature, float* S_ws, float* row_stats, float* row_loss, float* loss, cseg_stream_t stream);
+int cseg_contrast_bwd_parts_cap(int Ncap, int D);
+int cseg_contrast_bwd_dn(const float* anchors, const int32_t* a_lab, const int32_t* header, int Ncap, int D, float temperature,
+                         const float* S_ws, const float* row_stats, const float* d_loss, float* d_anchor_parts, cseg_stream_t stream);
+int cseg_scatter_anchor_grad_dn(const float* d_anchor_parts, const int32_t* sel_pix, const int32_t* header, int Ncap, int B, int D,
+                                int P, float scale, float* d_embed, cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * HRNet head input: bilinear(align_corners=True) upsample of the low-resolution maps to the first map's size
