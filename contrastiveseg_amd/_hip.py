@@ -171,6 +171,13 @@ SIGNATURES = {
     "cseg_rmi_solve": (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr]),
     "cseg_rmi_finish": (_c_int, [_ptr, _c_int, _ptr, _c_int, _c_int, _c_float, _c_int, _c_float, _ptr, _ptr, _ptr]),
     "cseg_rmi_bwd": (_c_int, [_ptr] * 9 + [_c_int] * 6 + [_c_float, _c_int, _c_float, _ptr, _ptr, _ptr]),
+    "cseg_lovasz_tiles": (_c_int, [ctypes.c_long]),
+    "cseg_lovasz_errors": (_c_int, [_ptr, _ptr] + [_c_int] * 9 + [_ptr] * 6),
+    "cseg_lovasz_pack": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),
+    "cseg_lovasz_order": (_c_int, [_ptr] * 5 + [_c_int, _c_int, _ptr]),
+    "cseg_lovasz_grad": (_c_int, [_ptr, _ptr, _c_int, _c_int] + [_ptr] * 6),
+    "cseg_lovasz_finish": (_c_int, [_ptr, _ptr, _c_int, _c_int] + [_ptr] * 4),
+    "cseg_lovasz_bwd": (_c_int, [_ptr] * 5 + [_c_int] * 6 + [_ptr] * 3),
     "cseg_conv_stat_segments":(ctypes.c_size_t, [_c_int] * 4),
     "cseg_conv3x3_split_fwd_st": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 7 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
     "cseg_conv1x1_split_fwd_st": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 5 + [_ptr, _ptr, _ptr, _ptr, _ptr]),

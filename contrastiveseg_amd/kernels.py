@@ -774,6 +774,160 @@ def rmi_loss(seg, target, lam=0.5, lambda_way=1, loss_weight=1.0, want_terms=Fal
 
 
 # ----------------------------------------------------------------------------------------------------------
+# segmentation term: upsample + softmax + Lovasz extension of the Jaccard loss (csrc/lovasz.hip)
+# ----------------------------------------------------------------------------------------------------------
+# Classes whose sort segments are in flight together: the ping-pong key / payload buffers are 16 bytes x chunk x P whatever K is
+# (DESIGN.md section 21). The result does not depend on it.
+LOVASZ_CLASS_CHUNK = 4
+LOVASZ_MAX_CLASSES = 256
+
+
+def _lovasz_shapes(what, seg, target):
+    if seg.dim() != 4 or target.dim() != 3 or target.shape[0] != seg.shape[0]:
+        raise RuntimeError("%s: seg %s / target %s, expected [B,K,h,w] / [B,H,W]" % (what, tuple(seg.shape), tuple(target.shape)))
+    B, K, h, w = seg.shape
+    _, H, W = target.shape
+    if B * H * W >= 2 ** 31:
+        raise RuntimeError("%s: %d label pixels (P = B * H * W must be below 2^31)" % (what, B * H * W))
+    if K > LOVASZ_MAX_CLASSES:
+        raise RuntimeError("%s: %d classes (at most %d are implemented)" % (what, K, LOVASZ_MAX_CLASSES))
+    if H < h or W < w:
+        raise RuntimeError("%s: only upsampling is supported (%dx%d -> %dx%d)" % (what, h, w, H, W))
+    return B, K, h, w, H, W, B * H * W
+
+
+def _lovasz_planes(what, P_shape, **planes):
+    for name, (t, dtype) in planes.items():
+        if t.dim() != 2 or tuple(t.shape) != tuple(P_shape):
+            raise RuntimeError("%s: %s is %s, expected [K,P] = %s" % (what, name, tuple(t.shape), tuple(P_shape)))
+    K, P = P_shape
+    if K < 1 or K > LOVASZ_MAX_CLASSES or P < 1 or P >= 2 ** 31:
+        raise RuntimeError("%s: [K,P] = %s (1 <= K <= %d classes, 1 <= P < 2^31)" % (what, tuple(P_shape), LOVASZ_MAX_CLASSES))
+    return [_p(t, dtype, name) for name, (t, dtype) in planes.items()]
+
+
+@torch.no_grad()
+def lovasz_errors(seg, target, ignore_index=-1, status=None):
+    """seg [B,K,h,w] f32 (coarse logits), target [B,H,W] i64 -> e f32 [K,P] = |fg - softmax(bilinear(seg))| per class at the P = B H W
+    label pixels (-1 at pixels whose label is not in [0, K)), fg u8 [K,P], counts i32 [K+2]: fg pixels per class, valid pixels, labels
+    that are neither `ignore_index` nor a class id (also added to status[1] when `status` i32 [4] is given)."""
+    B, K, h, w, H, W, P = _lovasz_shapes("lovasz_errors", seg, target)
+    seg, target = seg.contiguous(), target.contiguous()
+    dev = seg.device
+    e = torch.empty(K, P, dtype=F32, device=dev)
+    fg = torch.empty(K, P, dtype=U8, device=dev)
+    counts = torch.empty(K + 2, dtype=I32, device=dev)
+    _hip.call("cseg_lovasz_errors", _p(seg, F32, "seg"), _p(target, I64, "target"), int(ignore_index), B, K, h, w, H, W, 0, K, _null(),
+              _pf(e), _pf(fg), _pf(counts), _p(status, I32, "status") if status is not None else _null(), _hip.stream_ptr())
+    return e, fg, counts
+
+
+def _lovasz_sort(keys):
+    """keys i32 [n,P] (the u32 sort keys) -> sorted in place, and the payload i32 [n,P]."""
+    n, P = keys.shape
+    T = _hip.lib().cseg_lovasz_tiles(P)
+    pay = torch.empty(n, P, dtype=I32, device=keys.device)
+    keys_b, pay_b = torch.empty_like(keys), torch.empty_like(pay)
+    hist = torch.empty(n * 16 * T, dtype=I32, device=keys.device)
+    _hip.call("cseg_lovasz_order", _pf(keys), _pf(pay), _pf(keys_b), _pf(pay_b), _pf(hist), n, P, _hip.stream_ptr())
+    return pay
+
+
+@torch.no_grad()
+def lovasz_order(e, fg):
+    """e f32 [K,P] (negative = invalid pixel), fg u8 [K,P] -> perm i32 [K,P]: per class the pixel indices in descending e, ascending
+    index among equal e, invalid pixels last: the indices of torch.sort(e, stable=True, descending=True)."""
+    ep, fp = _lovasz_planes("lovasz_order", e.shape, e=(e, F32), fg=(fg, U8))
+    K, P = e.shape
+    keys = torch.empty(K, P, dtype=I32, device=e.device)
+    _hip.call("cseg_lovasz_pack", ep, fp, _null(), K, P, _pf(keys), _hip.stream_ptr())
+    return _lovasz_sort(keys)
+
+
+@torch.no_grad()
+def lovasz_grad(fg, perm, e):
+    """fg u8 [K,P], perm i32 [K,P] (lovasz_order), e f32 [K,P] -> g f64 [K,P]: lovasz_grad(fg[perm]) of the reference in sorted order
+    (zero for a class without fg pixels), and loss_c f64 [K] = sum_r e[perm][r] g[r]."""
+    ep, fp, pp = _lovasz_planes("lovasz_grad", fg.shape, e=(e, F32), fg=(fg, U8), perm=(perm, I32))
+    K, P = fg.shape
+    dev = fg.device
+    T = _hip.lib().cseg_lovasz_tiles(P)
+    keys = torch.empty(K, P, dtype=I32, device=dev)
+    _hip.call("cseg_lovasz_pack", ep, fp, pp, K, P, _pf(keys), _hip.stream_ptr())
+    toff = torch.empty(K, T, dtype=I32, device=dev)
+    gtot = torch.empty(K, dtype=I32, device=dev)
+    partial = torch.empty(K, T, dtype=F64, device=dev)
+    g = torch.empty(K, P, dtype=F64, device=dev)
+    loss_c = torch.empty(K, dtype=F64, device=dev)
+    outd = torch.empty(2, dtype=F64, device=dev)
+    out = torch.empty(1, dtype=F32, device=dev)
+    _hip.call("cseg_lovasz_grad", _pf(keys), _null(), K, P, _pf(toff), _pf(gtot), _pf(g), _null(), _pf(partial), _hip.stream_ptr())
+    _hip.call("cseg_lovasz_finish", _pf(partial), _pf(gtot), K, P, _pf(loss_c), _pf(outd), _pf(out), _hip.stream_ptr())
+    return g, loss_c
+
+
+class UpsampleLovasz(Function):
+    """lovasz_softmax_flat(*flatten_probas(softmax(F.interpolate(seg, target.shape, bilinear, align_corners=True)), target, ignore),
+    only_present=True) of the reference (lib/loss/lovasz_loss.py:216-267) with the validity rule 0 <= label < K. No host
+    synchronisation; classes go through the sort LOVASZ_CLASS_CHUNK at a time. Saved for the backward: G_buf [K,P] f32 (d term_c / d p
+    per pixel), the one buffer of the size of the upsampled logits; without a gradient to compute it is neither allocated nor written."""
+
+    @staticmethod
+    def forward(ctx, seg, target, ignore_index, status, want_grad):
+        B, K, h, w, H, W, P = _lovasz_shapes("lovasz_softmax", seg, target)
+        seg, target = seg.contiguous(), target.contiguous()
+        sp, tp = _p(seg, F32, "seg"), _p(target, I64, "target")
+        stp = _p(status, I32, "status") if status is not None else _null()
+        dev = seg.device
+        T = _hip.lib().cseg_lovasz_tiles(P)
+        chunk = max(1, min(int(LOVASZ_CLASS_CHUNK), K))
+        keys_a, keys_b, pay_a, pay_b = (torch.empty(chunk, P, dtype=I32, device=dev) for _ in range(4))
+        hist = torch.empty(chunk * 16 * T, dtype=I32, device=dev)
+        toff = torch.empty(K, T, dtype=I32, device=dev)
+        gtot = torch.empty(K, dtype=I32, device=dev)
+        partial = torch.empty(K, T, dtype=F64, device=dev)
+        gbuf = torch.empty(K, P, dtype=F32, device=dev) if want_grad else None
+        stream = _hip.stream_ptr()
+        for k0 in range(0, K, chunk):
+            kn = min(chunk, K - k0)
+            _hip.call("cseg_lovasz_errors", sp, tp, int(ignore_index), B, K, h, w, H, W, k0, kn, _pf(keys_a), _null(), _null(), _null(),
+                      stp if k0 == 0 else _null(), stream)
+            _hip.call("cseg_lovasz_order", _pf(keys_a), _pf(pay_a), _pf(keys_b), _pf(pay_b), _pf(hist), kn, P, stream)
+            _hip.call("cseg_lovasz_grad", _pf(keys_a), _pf(pay_a), kn, P, _pf(toff[k0:]), _pf(gtot[k0:]), _null(),
+                      _pf(gbuf[k0:]) if gbuf is not None else _null(), _pf(partial[k0:]), stream)
+        outd = torch.empty(2, dtype=F64, device=dev)
+        out = torch.empty(1, dtype=F32, device=dev)
+        _hip.call("cseg_lovasz_finish", _pf(partial), _pf(gtot), K, P, _null(), _pf(outd), _pf(out), stream)
+        if gbuf is not None:
+            ctx.save_for_backward(seg, target, gbuf, outd)
+        ctx.mark_non_differentiable(outd)
+        return out[0].clone(), outd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_outd):
+        seg, target, gbuf, outd = ctx.saved_tensors
+        B, K, h, w = seg.shape
+        _, H, W = target.shape
+        d_seg = torch.empty_like(seg)
+        stats = torch.empty(3, B * H * W, dtype=F32, device=seg.device)
+        g = g.reshape(1).to(F32).contiguous()
+        _hip.call("cseg_lovasz_bwd", _p(seg, F32, "seg"), _p(target, I64, "target"), _pf(gbuf), _pf(outd), _p(g, F32, "d_loss"), B, K, h, w,
+                  H, W, _pf(stats), _pf(d_seg), _hip.stream_ptr())
+        return d_seg, None, None, None, None
+
+
+def lovasz_softmax(seg, target, want_terms=False, ignore_index=-1, status=None):
+    """The Lovasz-softmax segmentation term (mean over the classes present among the valid pixels) on coarse or label-resolution
+    logits. With want_terms also the f64 [2] device tensor {term, present classes}. Labels that are neither `ignore_index` nor in
+    [0, K) are dropped and counted in status[1] (i32 [4], optional). No valid pixel at all: the term and its gradient are exactly 0 (the
+    reference returns an empty tensor there). Works under torch.no_grad()."""
+    # (inside Function.forward the grad mode is off and needs_input_grad does not see torch.no_grad(): decided here)
+    loss, outd = UpsampleLovasz.apply(seg, target, ignore_index, status, torch.is_grad_enabled() and seg.requires_grad)
+    return (loss, outd) if want_terms else loss
+
+
+# ----------------------------------------------------------------------------------------------------------
 # test phase: multi-scale + flip fusion with the argmax, confusion matrix (csrc/ms_eval.hip)
 # ----------------------------------------------------------------------------------------------------------
 MS_MAX_TERMS = 8

@@ -104,3 +104,47 @@ class FSAuxRMILoss(nn.Module):
         seg_loss = self.rmi_loss(seg_out, targets)
         lw = self.configer.get("network", "loss_weights")
         return lw["seg_loss"] * seg_loss + lw["aux_loss"] * aux_loss
+
+
+class FSCELOVASZLoss(nn.Module):
+    """CE + Lovasz-softmax on the segmentation map (reference :77-124, lib/loss/lovasz_loss.py:216-267): the fused upsample+CE kernel
+    plus the sort + scan kernels of csrc/lovasz.hip, both on the coarse logits. Same constructor contract as FSCELoss (ce_weight,
+    ce_reduction, ce_ignore_index; the weights apply to the CE part only, as in the reference). The reference's list / tuple branch
+    (CE only, no Lovasz term) has no caller in this package and is refused."""
+
+    def __init__(self, configer=None):
+        super(FSCELOVASZLoss, self).__init__()
+        self.configer = configer
+        self.ce_loss = FSCELoss(self.configer)
+        self.ignore_index = self.ce_loss.ignore_index
+
+    def bad_label_count(self, reset=True):
+        """FSCELoss.bad_label_count of the CE part: both parts see the same labels and drop the same ones; the CE kernel counts."""
+        return self.ce_loss.bad_label_count(reset)
+
+    def forward(self, inputs, *targets, weights=None, **kwargs):
+        if isinstance(inputs, dict) and "seg" in inputs:
+            inputs = inputs["seg"]
+        if isinstance(inputs, (tuple, list)):
+            raise NotImplementedError("FSCELOVASZLoss: a list / tuple of maps (the reference applies CE only there) is not "
+                                      "implemented; pass the segmentation map or a dict with 'seg'")
+        return self.ce_loss(inputs, targets[0]) + K.lovasz_softmax(inputs, targets[0], ignore_index=self.ignore_index)
+
+
+class FSAuxCELOVASZLoss(nn.Module):
+    """(ce + lovasz)(seg) * w_seg + ce(aux) * w_aux: the analogue of FSAuxRMILoss. The reference has no such class -- its only
+    Lovasz criterion for the contrast losses is FSCELOVASZLoss in the registered memory criterion; this is the project's own composite
+    for mem_contrast_auxce_loss (the DeepLab / OCR memory models, whose auxiliary map gets the plain CE as everywhere else)."""
+
+    def __init__(self, configer=None):
+        super(FSAuxCELOVASZLoss, self).__init__()
+        self.configer = configer
+        self.ce_loss = FSCELoss(self.configer)
+        self.lovasz_loss = FSCELOVASZLoss(self.configer)
+
+    def forward(self, inputs, targets, **kwargs):
+        aux_out, seg_out = inputs
+        aux_loss = self.ce_loss(aux_out, targets)
+        seg_loss = self.lovasz_loss(seg_out, targets)
+        lw = self.configer.get("network", "loss_weights")
+        return lw["seg_loss"] * seg_loss + lw["aux_loss"] * aux_loss

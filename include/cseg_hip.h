@@ -763,6 +763,38 @@ int cseg_rmi_bwd(const float* seg, const int64_t* target, const float* p_pool, c
                  const double* means, const double* grads, const double* outd, const float* d_loss, int B, int K, int h, int w,
                  int H, int W, float lam, int lambda_way, float loss_weight, float* g_pool, float* d_seg, cseg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Lovasz-softmax segmentation term (csrc/lovasz.hip).  Replaces lovasz_softmax_flat(*flatten_probas(softmax(F.interpolate(seg, (H, W),
+ * bilinear, align_corners=True)), target, ignore), only_present=True) (lib/loss/lovasz_loss.py:216-267) as a segmented radix sort and a
+ * segmented scan; nothing depends on data on the host, no block waits for another one.  P = B * H * W < 2^31, K <= 256, H >= h, W >= w.
+ * A pixel is valid when 0 <= label < K.  Order per class: descending e = |fg - p|, ascending flat pixel index among equal e; invalid
+ * pixels stay in place and sort after every valid one.  Sort key u32: bit 0 = fg, bits 1..30 = 0x3F800000 - bits(e), or 0x3F800001 for
+ * an invalid pixel.  T = cseg_lovasz_tiles(P) sort tiles per class.  Deterministic.
+ *
+ *   cseg_lovasz_errors  classes [k0, k0 + kn): keys [kn,P] (or NULL), e [K,P] f32 (-1 at invalid pixels) and fg [K,P] u8 (or NULL; rows
+ *                       k0 .. k0 + kn - 1 are written), counts [K+2] i32 (or NULL; zeroed here: fg pixels per class, valid pixels, labels
+ *                       that are neither ignore_label nor in [0, K)), status (or NULL): status[1] += that last count.
+ *   cseg_lovasz_pack    keys[c][r] = key of (e, fg)[c][perm[c][r]], perm NULL = identity; e < 0 marks an invalid pixel.
+ *   cseg_lovasz_order   sorts n segments of P keys (payload = position before the sort) in place: keys_a / pay_a hold the result (pay_a
+ *                       need not be initialised), keys_b / pay_b [n,P] and hist [n * 16 * T] i32 are scratch.
+ *   cseg_lovasz_grad    sorted keys -> toff [n,T] i32 (scratch), gtot [n] i32 (fg per class), partial [n,T] f64 (sums of e_(r) g_r),
+ *                       g_sorted [n,P] f64 (or NULL), gbuf [n,P] f32 (or NULL; needs pay): d term_c / d p at the pixel, every word written.
+ *   cseg_lovasz_finish  -> loss_c [K] f64 (or NULL), outd [2] f64 {term, present classes}, out [1] f32.
+ *   cseg_lovasz_bwd     gbuf [K,P], d_loss [1] f32 (device), stats [3,P] f32 scratch -> d_seg [B,K,h,w] f32.
+ * ------------------------------------------------------------------------------------------------ */
+int cseg_lovasz_tiles(long P);
+int cseg_lovasz_errors(const float* seg, const int64_t* target, int ignore_label, int B, int K, int h, int w, int H, int W, int k0,
+                       int kn, uint32_t* keys, float* e, uint8_t* fg, int32_t* counts, int32_t* status, cseg_stream_t stream);
+int cseg_lovasz_pack(const float* e, const uint8_t* fg, const int32_t* perm, int n, int P, uint32_t* keys, cseg_stream_t stream);
+int cseg_lovasz_order(uint32_t* keys_a, int32_t* pay_a, uint32_t* keys_b, int32_t* pay_b, int32_t* hist, int n, int P,
+                      cseg_stream_t stream);
+int cseg_lovasz_grad(const uint32_t* keys, const int32_t* pay, int n, int P, int32_t* toff, int32_t* gtot, double* g_sorted,
+                     float* gbuf, double* partial, cseg_stream_t stream);
+int cseg_lovasz_finish(const double* partial, const int32_t* gtot, int K, int P, double* loss_c, double* outd, float* out,
+                       cseg_stream_t stream);
+int cseg_lovasz_bwd(const float* seg, const int64_t* target, const float* gbuf, const double* outd, const float* d_loss, int B, int K,
+                    int h, int w, int H, int W, float* stats, float* d_seg, cseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
