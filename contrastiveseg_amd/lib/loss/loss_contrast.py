@@ -38,7 +38,8 @@ import torch.nn as nn
 from contrastiveseg_amd import _host
 from contrastiveseg_amd import kernels as K
 from contrastiveseg_amd.lib.loss.anchor_sampling import plan_selection
-from contrastiveseg_amd.lib.loss.loss_helper import FSAuxCELoss, FSAuxRMILoss, FSCELoss, FSRMILoss
+from contrastiveseg_amd.lib.loss.loss_helper import (FSAuxCELOVASZLoss, FSAuxCELoss, FSAuxRMILoss, FSCELOVASZLoss, FSCELoss,
+                                                     FSRMILoss)
 from contrastiveseg_amd.lib.utils import distributed as D
 from contrastiveseg_amd.lib.utils.tools.logger import Logger as Log
 
@@ -126,25 +127,48 @@ class PixelContrastLoss(nn.Module, ABC):
         self.sampling_sticky = None  # i32 [1] on the device: OR of the status bits of every step (Trainer._display reads it)
 
     # -- mining ------------------------------------------------------------------------------------------
-    def _mine(self, feats, labels, predict, seg, seg_ready=None, gather=False):
-        """Runs cseg_classify_partition. With `seg_ready` (a HIP event recorded right after the logits were produced,
-        see nets/hrnet.py) the kernels and the counts D2H copy go to a side stream, so they -- and the host-side
-        selection plan that follows -- overlap the projection head still running on the compute stream."""
-        B, Dm, h, w = feats.shape
+    def _classify(self, feats, labels, predict, seg, prezeroed=False):
+        """The one cseg_classify_partition call. `prezeroed` (device sampling) is passed on only when set: the CPU restatement of the
+        kernels module (oracle/cpu_port.py) has no such argument."""
+        kw = {"prezeroed": True} if prezeroed else {}
+        if seg is not None:
+            return K.classify_partition(labels, self.ignore_label, seg=seg, **kw)
+        return K.classify_partition(labels, self.ignore_label, predict=predict.contiguous(),
+                                    num_classes=self.configer.get('data', 'num_classes'), feat_hw=tuple(feats.shape[2:]), **kw)
 
-        def run():
-            if seg is not None:
-                return K.classify_partition(labels, self.ignore_label, seg=seg)
-            return K.classify_partition(labels, self.ignore_label, predict=predict.contiguous(),
-                                        num_classes=self.configer.get('data', 'num_classes'), feat_hw=(h, w))
-        if seg_ready is None or seg is None or not seg.is_cuda:
-            return run()
+    @staticmethod
+    def _overlaps(seg_ready, seg):
+        """Whether mining goes to the side stream: the model recorded `seg_ready` (a HIP event, right after the logits were produced,
+        see nets/hrnet.py) and the logits are on the GPU. Otherwise it is a plain call on the current stream."""
+        return seg_ready is not None and seg is not None and seg.is_cuda
+
+    def _fork_join(self, seg_ready, seg, labels, run):
+        """Runs `run()` on the side stream behind `seg_ready` and joins the compute stream behind it, so that what `run` enqueues --
+        and any host work that follows -- overlaps the projection head still running on the compute stream. `run` returns
+        (result, tensors it produced that the compute stream consumes); returns (result, the event recorded behind the work)."""
         if self._side is None:
             self._side = torch.cuda.Stream(device=seg.device)
         main = torch.cuda.current_stream(seg.device)
         with torch.cuda.stream(self._side):
             self._side.wait_event(seg_ready)
-            cp = run()
+            result, consumed = run()
+            done = torch.cuda.Event()
+            done.record(self._side)
+        for t in consumed:
+            t.record_stream(main)                # produced on the side stream, consumed on the compute stream
+        seg.record_stream(self._side)
+        labels.record_stream(self._side)
+        main.wait_event(done)
+        return result, done
+
+    def _mine(self, feats, labels, predict, seg, seg_ready=None, gather=False):
+        """Runs cseg_classify_partition. With `seg_ready` the kernels and the counts D2H copy go to the side stream (_fork_join), so
+        they -- and the host-side selection plan that follows -- overlap the projection head."""
+        if not self._overlaps(seg_ready, seg):
+            return self._classify(feats, labels, predict, seg)
+
+        def run():
+            cp = self._classify(feats, labels, predict, seg)
             flat = torch.cat([cp["counts"].reshape(-1), cp["status"]])
             if gather:
                 # cross-rank contrast set: the all-gather of the per-rank counts is issued HERE, on the side stream, so that it -- like
@@ -153,13 +177,8 @@ class PixelContrastLoss(nn.Module, ABC):
                 flat = D.all_gather_cat(flat.unsqueeze(0))
             host = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
             host.copy_(flat, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(self._side)
-        for t in cp.values():
-            t.record_stream(main)                # produced on the side stream, consumed on the compute stream
-        seg.record_stream(self._side)
-        labels.record_stream(self._side)
-        main.wait_event(done)
+            return (cp, host), list(cp.values())
+        (cp, host), done = self._fork_join(seg_ready, seg, labels, run)
         cp["host_counts_global" if gather else "host_counts"] = (host, done)
         return cp
 
@@ -194,48 +213,30 @@ class PixelContrastLoss(nn.Module, ABC):
     def _forward_device(self, feats, labels, predict, seg, seg_ready):
         """Mining, selection, gather, contrast: all enqueued, nothing read back. Mining and planning keep the side-stream fork and
         join of _mine when the model recorded `seg_ready`."""
-        B, Dm, h, w = feats.shape
-        dev = feats.device
-        rng = self._rng_on(dev)
+        rng = self._rng_on(feats.device)
 
         def run():
-            if seg is not None:
-                cp = K.classify_partition(labels, self.ignore_label, seg=seg, prezeroed=True)
-            else:
-                cp = K.classify_partition(labels, self.ignore_label, predict=predict.contiguous(),
-                                          num_classes=self.configer.get('data', 'num_classes'), feat_hw=(h, w), prezeroed=True)
-            return cp, K.sample_anchors(cp, self.max_samples, self.max_views, rng, self.sampling_sticky)
-        if seg_ready is None or seg is None or not seg.is_cuda:
-            cp, (sel_pos, a_lab, header) = run()
+            cp = self._classify(feats, labels, predict, seg, prezeroed=True)
+            out = (cp["part_idx"],) + tuple(K.sample_anchors(cp, self.max_samples, self.max_views, rng, self.sampling_sticky))
+            return out, out
+        if self._overlaps(seg_ready, seg):
+            (part_idx, sel_pos, a_lab, header), _ = self._fork_join(seg_ready, seg, labels, run)
         else:
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=dev)
-            main = torch.cuda.current_stream(dev)
-            with torch.cuda.stream(self._side):
-                self._side.wait_event(seg_ready)
-                cp, (sel_pos, a_lab, header) = run()
-                done = torch.cuda.Event()
-                done.record(self._side)
-            for t in (cp["part_idx"], sel_pos, a_lab, header):
-                t.record_stream(main)
-            seg.record_stream(self._side)
-            labels.record_stream(self._side)
-            main.wait_event(done)
-        loss, sel_pix = K.PixelContrastDevice.apply(feats, cp["part_idx"], sel_pos, a_lab, header, self.temperature,
+            (part_idx, sel_pos, a_lab, header), _ = run()
+        loss, sel_pix = K.PixelContrastDevice.apply(feats, part_idx, sel_pos, a_lab, header, self.temperature,
                                                     self.base_temperature, _grad_slot(feats))
         self.last_selection = {"sel_pix": sel_pix, "header": header, "plan": None}
         return loss
 
     # -- forward -----------------------------------------------------------------------------------------
-    def forward(self, feats, labels=None, predict=None, seg=None, seg_ready=None):
+    def forward(self, feats, labels=None, predict=None, seg=None, seg_ready=None, segment_queue=None, pixel_queue=None):
         """feats [B,D,h,w] (L2-normalised embeddings), labels [B,H,W] long, and either `predict` [B,h,w] long
         (reference signature, loss_contrast.py:130) or `seg` [B,K,h,w] logits (argmax fused into the mining
-        kernel)."""
+        kernel). With the two queues (loss_contrast_mem.PixelContrastLoss passes them) the contrast set is the memory bank: a
+        rank's own anchors against its own copy of the bank, whatever `cross_rank` says."""
         assert labels is not None and (predict is not None or seg is not None)
-        B, Dm, h, w = feats.shape
-        P = h * w
         world = D.get_world_size()
-        cross = (world > 1 or D.exercise_single_rank()) and self.cross_rank
+        cross = segment_queue is None and (world > 1 or D.exercise_single_rank()) and self.cross_rank
         if self.device_sampling:
             if cross:
                 raise NotImplementedError("contrast.device_sampling with contrast.cross_rank on more than one rank (or under "
@@ -243,13 +244,21 @@ class PixelContrastLoss(nn.Module, ABC):
             return self._forward_device(feats, labels, predict, seg, seg_ready)
         cp = self._mine(feats, labels, predict, seg, seg_ready, gather=cross)
         if cross:
-            return self._forward_cross_rank(feats, cp, P, world)
+            return self._forward_cross_rank(feats, cp, feats.shape[2] * feats.shape[3], world)
         plan = self._plan(_counts_to_host(cp))
+        if segment_queue is None:
+            return self._forward_plan(feats, cp, plan, "self")
+        return self._forward_plan(feats, cp, plan, "bank", segment_queue.contiguous(), pixel_queue.contiguous())
+
+    def _forward_plan(self, feats, cp, plan, mode, segment_queue=None, pixel_queue=None):
+        """The local contrast term of a host plan: the picks to the device, gather + contrast against the anchors themselves
+        (mode "self") or the memory bank ("bank", read in place)."""
+        P = feats.shape[2] * feats.shape[3]
         dev = feats.device
         sel_pos = torch.from_numpy(plan.row_img.astype(np.int32) * P + plan.row_off).to(dev, non_blocking=True)
         a_lab = torch.from_numpy(plan.row_lab.astype(np.int32)).to(dev, non_blocking=True)
-        loss, sel_pix = K.PixelContrast.apply(feats, cp["part_idx"], sel_pos, a_lab, "self", self.temperature,
-                                              self.base_temperature, None, None, _grad_slot(feats))
+        loss, sel_pix = K.PixelContrast.apply(feats, cp["part_idx"], sel_pos, a_lab, mode, self.temperature,
+                                              self.base_temperature, segment_queue, pixel_queue, _grad_slot(feats))
         self.last_selection = {"sel_pix": sel_pix, "plan": plan}
         return loss
 
@@ -302,9 +311,22 @@ class PixelContrastLoss(nn.Module, ABC):
         return loss
 
 
-class ContrastCELoss(nn.Module, ABC):
+# the segmentation criterion of the composite criteria: [takes the auxiliary map too][term]. 'rmi' without an auxiliary map: the
+# reference constructs FSAuxRMILoss there and unpacks the single logit tensor as a pair, which cannot run; FSRMILoss is what it sets
+# out to be
+SEG_CRITERIA = {False: {"ce": FSCELoss, "rmi": FSRMILoss, "lovasz": FSCELOVASZLoss},
+                True: {"ce": FSAuxCELoss, "rmi": FSAuxRMILoss, "lovasz": FSAuxCELOVASZLoss}}
+
+
+class _ContrastComposite(nn.Module, ABC):
+    """seg_criterion(seg | [seg_aux, seg]) + loss_weight * contrast_criterion(embed): the four registered contrast criteria (this
+    module and loss_contrast_mem.py) are this class with other data."""
+    aux = False                          # the segmentation criterion takes [seg_aux, seg]
+    contrast_class = PixelContrastLoss   # the memory pair: loss_contrast_mem.PixelContrastLoss
+    reads_lovasz = False                 # the memory pair reads contrast.use_lovasz too (the reference's bank-free pair has no such switch)
+
     def __init__(self, configer=None):
-        super(ContrastCELoss, self).__init__()
+        super(_ContrastComposite, self).__init__()
         self.configer = configer
         ignore_index = -1
         if self.configer.exists('loss', 'params') and 'ce_ignore_index' in self.configer.get('loss', 'params'):
@@ -312,18 +334,34 @@ class ContrastCELoss(nn.Module, ABC):
         Log.info('ignore_index: {}'.format(ignore_index))
         self.loss_weight = self.configer.get('contrast', 'loss_weight')
         self.use_rmi = self.configer.get('contrast', 'use_rmi')
-        # use_rmi: the reference constructs FSAuxRMILoss here and unpacks the single logit tensor as a pair, which cannot run;
-        # this criterion has no auxiliary map, so it takes FSRMILoss
-        self.seg_criterion = FSRMILoss(configer=configer) if self.use_rmi else FSCELoss(configer=configer)
-        self.contrast_criterion = PixelContrastLoss(configer=configer)
+        term = "rmi" if self.use_rmi else "ce"
+        if self.reads_lovasz:
+            self.use_lovasz = self.configer.get('contrast', 'use_lovasz') \
+                if self.configer.exists('contrast', 'use_lovasz') else False
+            if self.use_lovasz and self.use_rmi:
+                raise NotImplementedError("contrast.use_lovasz together with contrast.use_rmi: the reference silently takes RMI there; "
+                                          "switch one of them off")
+            if self.use_lovasz:
+                term = "lovasz"
+        self.seg_criterion = SEG_CRITERIA[self.aux][term](configer=configer)
+        self.contrast_criterion = self.contrast_class(configer=configer)
 
     def forward(self, preds, target, with_embed=False):
         assert "seg" in preds
+        if self.aux:
+            assert "seg_aux" in preds
         assert "embed" in preds
         seg = preds['seg']
-        embedding = preds['embed']
-        loss = self.seg_criterion(seg, target)                       # upsample fused into the CE kernel
-        loss_contrast = self.contrast_criterion(embedding, target, seg=seg, seg_ready=preds.get('seg_ready'))
+        loss = self.seg_criterion([preds['seg_aux'], seg] if self.aux else seg, target)   # upsample fused into the CE kernel
+        queues = {}
+        if self.contrast_class.uses_memory_bank:
+            queues = {k: preds.get(k) for k in ('segment_queue', 'pixel_queue')}
+        if None in queues.values():
+            # no queues in `preds` (the validation pass: seg_net(..., is_eval=True) returns seg / embed only): the reference's
+            # `loss + 0 * 0` -- a zero scalar on the loss's device, made there without a host round trip
+            loss_contrast = loss.new_zeros(())
+        else:
+            loss_contrast = self.contrast_criterion(preds['embed'], target, seg=seg, seg_ready=preds.get('seg_ready'), **queues)
         # the two terms of the last call, detached (no host sync): the segmentation term is a smooth function of the weights, the
         # contrastive term is not (argmax decides hard / easy, rounding-level changes of the logits move anchors between the sets) --
         # tests that compare two implementations after an SGD step bound the former tightly and the latter loosely
@@ -333,32 +371,10 @@ class ContrastCELoss(nn.Module, ABC):
         return loss + 0 * loss_contrast  # same trick as the reference: keeps every parameter in the DDP graph
 
 
-class ContrastAuxCELoss(nn.Module, ABC):
-    def __init__(self, configer=None):
-        super(ContrastAuxCELoss, self).__init__()
-        self.configer = configer
-        ignore_index = -1
-        if self.configer.exists('loss', 'params') and 'ce_ignore_index' in self.configer.get('loss', 'params'):
-            ignore_index = self.configer.get('loss', 'params')['ce_ignore_index']
-        Log.info('ignore_index: {}'.format(ignore_index))
-        self.loss_weight = self.configer.get('contrast', 'loss_weight')
-        self.use_rmi = self.configer.get('contrast', 'use_rmi')
-        self.seg_criterion = FSAuxRMILoss(configer=configer) if self.use_rmi else FSAuxCELoss(configer=configer)
-        self.contrast_criterion = PixelContrastLoss(configer=configer)
+class ContrastCELoss(_ContrastComposite):
+    """'contrast_ce_loss' (reference lib/loss/loss_contrast.py:150-189)."""
 
-    def forward(self, preds, target, with_embed=False):
-        assert "seg" in preds
-        assert "seg_aux" in preds
-        assert "embed" in preds
-        seg = preds['seg']
-        seg_aux = preds['seg_aux']
-        embedding = preds['embed']
-        loss = self.seg_criterion([seg_aux, seg], target)
-        loss_contrast = self.contrast_criterion(embedding, target, seg=seg, seg_ready=preds.get('seg_ready'))
-        # the two terms of the last call, detached (no host sync): the segmentation term is a smooth function of the weights, the
-        # contrastive term is not (argmax decides hard / easy, rounding-level changes of the logits move anchors between the sets) --
-        # tests that compare two implementations after an SGD step bound the former tightly and the latter loosely
-        self.last_terms = (loss.detach(), loss_contrast.detach())
-        if with_embed is True:
-            return loss + self.loss_weight * loss_contrast
-        return loss + 0 * loss_contrast
+
+class ContrastAuxCELoss(_ContrastComposite):
+    """'contrast_auxce_loss' (reference :192-234)."""
+    aux = True

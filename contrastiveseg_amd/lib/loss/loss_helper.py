@@ -42,7 +42,7 @@ class FSCELoss(nn.Module):
     def bad_label_count(self, reset=True):
         """Labels seen since the last call that are neither `ce_ignore_index` nor a class id: the kernel drops them
         (nn.CrossEntropyLoss of the reference would assert). One D2H copy: call it where the host syncs anyway
-        (Trainer._display does, and raises)."""
+        (Trainer._display reads the same counters through bad_label_total, with the loss, and raises)."""
         n = int(self.status[1])
         if reset:
             self.status.zero_()
@@ -60,22 +60,6 @@ class FSCELoss(nn.Module):
         return self._one(inputs, targets[0])
 
 
-class FSAuxCELoss(nn.Module):
-    """seg_loss * w_seg + aux_loss * w_aux (reference :301-313)."""
-
-    def __init__(self, configer=None):
-        super(FSAuxCELoss, self).__init__()
-        self.configer = configer
-        self.ce_loss = FSCELoss(self.configer)
-
-    def forward(self, inputs, targets, **kwargs):
-        aux_out, seg_out = inputs
-        seg_loss = self.ce_loss(seg_out, targets)
-        aux_loss = self.ce_loss(aux_out, targets)
-        lw = self.configer.get("network", "loss_weights")
-        return lw["seg_loss"] * seg_loss + lw["aux_loss"] * aux_loss
-
-
 class FSRMILoss(nn.Module):
     """RMILoss on the segmentation map (reference :360-369)."""
 
@@ -86,24 +70,6 @@ class FSRMILoss(nn.Module):
 
     def forward(self, inputs, targets, **kwargs):
         return self.rmi_loss(inputs, targets)
-
-
-class FSAuxRMILoss(nn.Module):
-    """rmi(seg) * w_seg + ce(aux) * w_aux (reference :316-329): CE on the auxiliary map through the fused upsample+CE kernel, RMI
-    on the segmentation map through the fused RMI kernels."""
-
-    def __init__(self, configer=None):
-        super(FSAuxRMILoss, self).__init__()
-        self.configer = configer
-        self.ce_loss = FSCELoss(self.configer)
-        self.rmi_loss = RMILoss(self.configer)
-
-    def forward(self, inputs, targets, **kwargs):
-        aux_out, seg_out = inputs
-        aux_loss = self.ce_loss(aux_out, targets)
-        seg_loss = self.rmi_loss(seg_out, targets)
-        lw = self.configer.get("network", "loss_weights")
-        return lw["seg_loss"] * seg_loss + lw["aux_loss"] * aux_loss
 
 
 class FSCELOVASZLoss(nn.Module):
@@ -131,20 +97,46 @@ class FSCELOVASZLoss(nn.Module):
         return self.ce_loss(inputs, targets[0]) + K.lovasz_softmax(inputs, targets[0], ignore_index=self.ignore_index)
 
 
-class FSAuxCELOVASZLoss(nn.Module):
-    """(ce + lovasz)(seg) * w_seg + ce(aux) * w_aux: the analogue of FSAuxRMILoss. The reference has no such class -- its only
-    Lovasz criterion for the contrast losses is FSCELOVASZLoss in the registered memory criterion; this is the project's own composite
-    for mem_contrast_auxce_loss (the DeepLab / OCR memory models, whose auxiliary map gets the plain CE as everywhere else)."""
+class _FSAuxLoss(nn.Module):
+    """term(seg) * w_seg + ce(aux) * w_aux (reference :301-329): `ce_loss` always takes the auxiliary map; the sub-module `seg_name`
+    takes the segmentation map -- `ce_loss` again, or an instance of `seg_class` built next to it."""
+    seg_name, seg_class = "ce_loss", None
 
     def __init__(self, configer=None):
-        super(FSAuxCELOVASZLoss, self).__init__()
+        super(_FSAuxLoss, self).__init__()
         self.configer = configer
         self.ce_loss = FSCELoss(self.configer)
-        self.lovasz_loss = FSCELOVASZLoss(self.configer)
+        if self.seg_class is not None:
+            setattr(self, self.seg_name, self.seg_class(self.configer))
 
     def forward(self, inputs, targets, **kwargs):
         aux_out, seg_out = inputs
+        seg_loss = getattr(self, self.seg_name)(seg_out, targets)
         aux_loss = self.ce_loss(aux_out, targets)
-        seg_loss = self.lovasz_loss(seg_out, targets)
         lw = self.configer.get("network", "loss_weights")
         return lw["seg_loss"] * seg_loss + lw["aux_loss"] * aux_loss
+
+
+class FSAuxCELoss(_FSAuxLoss):
+    """ce(seg) * w_seg + ce(aux) * w_aux (reference :301-313)."""
+
+
+class FSAuxRMILoss(_FSAuxLoss):
+    """rmi(seg) * w_seg + ce(aux) * w_aux (reference :316-329): CE on the auxiliary map through the fused upsample+CE kernel, RMI
+    on the segmentation map through the fused RMI kernels."""
+    seg_name, seg_class = "rmi_loss", RMILoss
+
+
+class FSAuxCELOVASZLoss(_FSAuxLoss):
+    """(ce + lovasz)(seg) * w_seg + ce(aux) * w_aux: the analogue of FSAuxRMILoss. The reference has no such class -- its only
+    Lovasz criterion for the contrast losses is FSCELOVASZLoss in the registered memory criterion; this is the project's own composite
+    for mem_contrast_auxce_loss (the DeepLab / OCR memory models, whose auxiliary map gets the plain CE as everywhere else)."""
+    seg_name, seg_class = "lovasz_loss", FSCELOVASZLoss
+
+
+def bad_label_total(criterion, device=None):
+    """Device scalar (int32, nothing read back): the labels the CE kernels under `criterion` dropped since their counters were last
+    reset, summed over the FSCELoss instances -- the modules that own a `status` counter (FSCELOVASZLoss and the aux composites
+    forward to theirs). `device`: where the zero lives when `criterion` holds no FSCELoss at all (contrast_ce_loss under use_rmi)."""
+    return sum((m.status[1] for m in criterion.modules() if isinstance(m, FSCELoss)),
+               torch.zeros((), dtype=torch.int32, device=device))

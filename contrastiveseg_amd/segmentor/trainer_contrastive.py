@@ -22,6 +22,7 @@ import torch.nn as nn
 from contrastiveseg_amd import _host
 from contrastiveseg_amd import kernels as K
 from contrastiveseg_amd.lib.loss.anchor_sampling import sampling_status_messages
+from contrastiveseg_amd.lib.loss.loss_helper import bad_label_total
 from contrastiveseg_amd.lib.loss.loss_manager import LossManager
 from contrastiveseg_amd.lib.metrics.running_score import RunningScore
 from contrastiveseg_amd.lib.models.model_manager import ModelManager
@@ -306,8 +307,7 @@ class Trainer(object):
         """The reference reduces the loss to rank 0 and calls .item() every step (:228-254); that is a host sync per
         step, so here it happens only when the line is printed."""
         c = self.configer
-        bad = sum((m.status[1] for m in self.pixel_loss.modules() if hasattr(m, 'bad_label_count')),
-                  torch.zeros((), dtype=torch.int32, device=self._last_loss.device))
+        bad = bad_label_total(self.pixel_loss, self._last_loss.device)
         disp = torch.stack([self._last_loss.float(), bad.float()])
         # contrast.device_sampling: the status bits the device planner collected since the criterion was built, one entry per bit (the
         # all-reduce below adds), in the same host read as the loss

@@ -392,32 +392,45 @@ def test_trainer_enqueue_on_gpu_matches_reference_golden(name, golden_dir):
 
 
 def test_side_stream_mining_is_equivalent():
-    """The overlap path (mining on a side HIP stream behind a 'seg ready' event) gives the same selection and loss."""
+    """The overlap path (mining on a side HIP stream behind a 'seg ready' event) gives the same selection and loss, for the three
+    users of PixelContrastLoss._fork_join at one case size (4 x 19 x 32 x 64 logits, 64-d embeddings): the bank-free criterion with
+    host sampling, the memory-bank criterion, and device sampling (its generator state comes from libcseg_host.so, as in
+    tests/test_gpu_device_sampling.py)."""
     dev = _dev()
     from contrastiveseg_amd.lib.loss.loss_manager import SEG_LOSS_DICT
-    c = LOSS_CASES["mid_self"]
-    target, seg, embed, _ = case_inputs(c)
-    crit = SEG_LOSS_DICT[c["loss"]](_configer(c)).to(dev)
-    t_target = torch.from_numpy(target).to(dev)
-    res = []
-    for use_event in (False, True, True):
-        t_seg = torch.from_numpy(seg).to(dev).requires_grad_(True)
-        t_embed = torch.from_numpy(embed).to(dev).requires_grad_(True)
-        preds = {"seg": t_seg, "embed": t_embed}
-        if use_event:
-            preds["seg_ready"] = torch.cuda.Event()
-            preds["seg_ready"].record()
-            _ = torch.randn(4096, 4096, device=dev) @ torch.randn(4096, 4096, device=dev)   # keep the main stream busy
-        torch.manual_seed(c["torch_seed"])
-        loss = crit(preds, t_target, with_embed=True)
-        loss.backward()
-        torch.cuda.synchronize()
-        res.append((float(loss.detach()), crit.contrast_criterion.last_selection["sel_pix"].cpu().numpy(),
-                    t_embed.grad.cpu().numpy(), t_seg.grad.cpu().numpy()))
-    for r in res[1:]:
-        assert r[0] == res[0][0]
-        assert np.array_equal(r[1], res[0][1])
-        assert np.array_equal(r[2], res[0][2]) and np.array_equal(r[3], res[0][3])
+    for case, device_sampling in (("mid_self", False), ("mem_v1", False), ("mid_self", True)):
+        c = LOSS_CASES[case]
+        target, seg, embed, extra = case_inputs(c)
+        cfg = _configer(c)
+        if device_sampling:
+            cfg.add(["contrast", "device_sampling"], True)
+        crit = SEG_LOSS_DICT[c["loss"]](cfg).to(dev)
+        assert crit.contrast_criterion.device_sampling is device_sampling
+        t_target = torch.from_numpy(target).to(dev)
+        res = []
+        for use_event in (False, True, True):
+            t_seg = torch.from_numpy(seg).to(dev).requires_grad_(True)
+            t_embed = torch.from_numpy(embed).to(dev).requires_grad_(True)
+            preds = {"seg": t_seg, "embed": t_embed}
+            for k, v in extra.items():
+                preds[k] = torch.from_numpy(v).to(dev)
+            if use_event:
+                preds["seg_ready"] = torch.cuda.Event()
+                preds["seg_ready"].record()
+                _ = torch.randn(4096, 4096, device=dev) @ torch.randn(4096, 4096, device=dev)   # keep the main stream busy
+            torch.manual_seed(c["torch_seed"])
+            crit.contrast_criterion.import_rng_from_torch()     # device sampling: the same stream again (the first call imports by itself)
+            loss = crit(preds, t_target, with_embed=True)
+            loss.backward()
+            torch.cuda.synchronize()
+            assert crit.contrast_criterion._side is not None or not use_event
+            res.append((float(loss.detach()), crit.contrast_criterion.last_selection["sel_pix"].cpu().numpy(),
+                        t_embed.grad.cpu().numpy(), t_seg.grad.cpu().numpy()))
+        assert np.isfinite(res[0][0]) and (res[0][1] >= 0).any() and np.abs(res[0][2]).max() > 0
+        for r in res[1:]:
+            assert r[0] == res[0][0], (case, device_sampling)
+            assert np.array_equal(r[1], res[0][1]), (case, device_sampling)
+            assert np.array_equal(r[2], res[0][2]) and np.array_equal(r[3], res[0][3]), (case, device_sampling)
 
 
 def test_contrast_bank_reference_config_size():
