@@ -73,6 +73,12 @@ SIGNATURES = {
     "cseg_contrast_bwd_parts_cap": (_c_int, [_c_int, _c_int]),
     "cseg_contrast_bwd_dn": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_float, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "cseg_scatter_anchor_grad_dn": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_float, _ptr, _ptr]),
+    "cseg_contrast_fwd_dn_bank": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int, _c_float, _c_float,
+                                           _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "cseg_contrast_bwd_parts_cap_bank": (_c_int, [_c_int, _c_int, _c_int]),
+    "cseg_contrast_bwd_dn_bank": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int, _c_float, _ptr, _ptr, _ptr,
+                                           _ptr, _ptr]),
+    "cseg_scatter_anchor_grad_dn_bank": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 5 + [_c_float, _ptr, _ptr]),
     "cseg_upcat_fwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),
     "cseg_upcat_fwd_amax": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr, _ptr]),
     "cseg_upcat_bwd": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),
@@ -88,6 +94,8 @@ SIGNATURES = {
     "cseg_queue_write_segments": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr]),
     "cseg_queue_write_pixels": (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _c_int,
                                          _ptr]),
+    "cseg_queue_enqueue_ws_ints": (ctypes.c_size_t, [_c_int] * 6),
+    "cseg_queue_enqueue_device": (_c_int, [_ptr, _ptr] + [_c_int] * 9 + [_ptr] * 8),
     "cseg_conv3x3_packed_floats": (ctypes.c_size_t, [_c_int, _c_int]),
     "cseg_conv3x3_pack_weights": (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr, _ptr]),
     "cseg_conv3x3_fwd": (_c_int, [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),

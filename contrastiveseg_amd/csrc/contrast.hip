@@ -889,6 +889,218 @@ __global__ __launch_bounds__(256) void bwd_dn_kernel(const float* __restrict__ S
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Device-N variants in BANK mode (contrast.device_bank): mode 2 of the kernels at the top of this file with
+// N = header[0] read on the device. The bank is read in place; M = K * 2 * ms is a host value, so the ColSrc comes from the host as for
+// cseg_contrast_fwd / cseg_contrast_bwd. Copies of s_gemm_kernel, row_pass_kernel and bwd_kernel<false> with another prologue and
+// epilogue, for the reason given above for the self-mode variants. The row stride of S is round32(M) as on the host path.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void s_gemm_dn_bank_kernel(const float* __restrict__ A, const int32_t* __restrict__ header, int Ncap,
+                                                             ColSrc col, float inv_tau, float* __restrict__ S, int ldS, int nJb) {
+    __shared__ __attribute__((aligned(16))) float As[SG_T * SG_LD];
+    __shared__ __attribute__((aligned(16))) float Cs[SG_T * SG_LD];
+    const int N = device_n(header, Ncap);
+    const int I0 = (blockIdx.x / nJb) * SG_T, J0 = (blockIdx.x % nJb) * SG_T;
+    if (I0 >= N) return;                             // (the grid of cseg_contrast_fwd has ceil(N / 64) row tiles)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wi = wave >> 1, wj = wave & 1;
+    const int h = lane >> 5, r32 = lane & 31;
+    const f32x16 acc = s_tile_64(A, N, col, I0, J0, As, Cs);
+    const int j = J0 + wj * 32 + r32;
+    if (j < ldS) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int ii = I0 + wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (ii < N) S[(size_t)ii * ldS + j] = acc[r] * inv_tau;
+        }
+    }
+}
+
+// row_pass_kernel for N = header[0] (the same statements)
+__global__ __launch_bounds__(256) void row_pass_dn_bank_kernel(const float* __restrict__ S, int ldS, const int32_t* __restrict__ header,
+                                                               ColSrc col, const int32_t* __restrict__ a_lab, float coef,
+                                                               float* __restrict__ row_stats, float* __restrict__ row_loss) {
+    __shared__ float red[4];
+    const int N = device_n(header, gridDim.x);         // (the grid is Ncap blocks)
+    const int i = blockIdx.x, tid = threadIdx.x;
+    if (i >= N) return;
+    const int M = col.M;
+    const float* row = S + (size_t)i * ldS;
+    const int yi = a_lab[i];
+    float m = -INFINITY;
+    for (int j = tid; j < M; j += 256) {
+        const float s = row[j];
+        m = (s > m || s != s) ? s : m;  // NaN propagates like torch.max
+    }
+    m = block_max(m, red, tid);
+    float neg = 0.f, cnt = 0.f;
+    for (int j = tid; j < M; j += 256) {
+        const int yj = col.label(j);
+        if (yj != yi) neg += expf(row[j] - m);
+        else if (j != i) cnt += 1.f;
+    }
+    neg = block_sum(neg, red, tid);
+    cnt = block_sum(cnt, red, tid);
+    float slp = 0.f, rs = 0.f;
+    for (int j = tid; j < M; j += 256) {
+        if (j != i && col.label(j) == yi) {
+            const float L = row[j] - m;
+            const float den = expf(L) + neg;
+            slp += L - logf(den);
+            rs += 1.f / den;
+        }
+    }
+    slp = block_sum(slp, red, tid);
+    rs = block_sum(rs, red, tid);
+    if (tid == 0) {
+        row_loss[i] = -coef * (slp / cnt);             // 0/0 -> NaN exactly like the reference (no positives)
+        float4 st = make_float4(m, neg, coef / ((float)N * cnt), rs);
+        *reinterpret_cast<float4*>(row_stats + 4 * (size_t)i) = st;
+    }
+}
+
+// bwd_kernel<false> for N = header[0] (the same statements; the split of the columns from bwd_splits(N, M, D) on the device). `parts`
+// is [nsplit_cap][Ncap][D]: tiles beyond N, splits beyond nsplit(N) and rows N <= ii < Ncap are written as zeros.
+__global__ __launch_bounds__(256) void bwd_dn_bank_kernel(const float* __restrict__ S, int ldS, const int32_t* __restrict__ header,
+                                                          int Ncap, ColSrc col, const int32_t* __restrict__ a_lab,
+                                                          const float* __restrict__ row_stats, const float* __restrict__ d_loss,
+                                                          float inv_tau, int nDg, float* __restrict__ parts) {
+    __shared__ float red[32][BW_DT * 32 + 4];
+    __shared__ __attribute__((aligned(16))) float cstage[4][32 * 32];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int h = lane >> 5, r32 = lane & 31;
+    const int It = blockIdx.x / nDg, dg = blockIdx.x % nDg;
+    const int split = blockIdx.y;
+    const int I0 = It * 32, d0 = dg * (BW_DT * 32);
+    const int M = col.M, D = col.D;
+    const int N = device_n(header, Ncap);
+    const int nsplit = N > 0 ? bwd_splits(N, M, D) : 0;
+    if (I0 >= N || split >= nsplit) {
+        for (int e = threadIdx.x; e < 32 * BW_DT * 32; e += 256) {
+            const int rr = e / (BW_DT * 32), cc = e - rr * (BW_DT * 32);
+            const int ii = I0 + rr, dd = d0 + cc;
+            if (ii < Ncap && dd < D) parts[((size_t)split * Ncap + ii) * D + dd] = 0.f;
+        }
+        return;
+    }
+    const int nJ = (M + 31) / 32, per_split = (nJ + nsplit - 1) / nsplit;
+    const int i = I0 + r32;
+    const bool i_ok = i < N;
+    const float4 sti = i_ok ? *reinterpret_cast<const float4*>(row_stats + 4 * (size_t)i)
+                            : make_float4(0.f, 1.f, 0.f, 0.f);
+    const int yi = i_ok ? a_lab[i] : -0x7ffffffe;
+
+    f32x16 acc[BW_DT];
+#pragma unroll
+    for (int t = 0; t < BW_DT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+    const int jt_lo = split * per_split, jt_hi = min(nJ, jt_lo + per_split);
+    for (int jt = jt_lo + wave; jt < jt_hi; jt += 4) {
+        const int J0 = jt * 32;
+        float hv[16];
+        // B operand: the 32 contrast rows of this column tile are staged feature tile by feature tile in a wave-private
+        // LDS block with coalesced 16-byte loads (8 lanes per 128-byte row segment) instead of 16 strided scalar loads
+        // per feature tile; missing rows (padding columns, zero tail of the bank) are staged as zeros.
+        const float* srow[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) srow[u] = col.row(J0 + (lane >> 3) + 8 * u);
+        float* cw = cstage[wave];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int jb = J0 + 8 * q + 4 * h;  // this lane's 4 consecutive columns for registers 4q..4q+3
+            const float4 s4 = i_ok ? ld4(S + (size_t)i * ldS + jb) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
+            const float* rp[4];
+            int lb[4];
+            col.decode4(jb, rp, lb);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int j = jb + t;
+                const int yj = lb[t];
+                const bool same = (yj == yi);
+                const bool pos = same && (j != i), neg = !same;
+                float g = grad_elem(sv[t], sti, pos, neg);
+                // a missing row (padding column or the zero tail of the bank) contributes 0 whatever H is
+                hv[4 * q + t] = (i_ok && rp[t]) ? g : 0.f;
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < BW_DT; ++t) {
+            const int dbase = d0 + t * 32 + (lane & 7) * 4;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float4 v = (srow[u] && dbase < D) ? ld4(srow[u] + dbase) : make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4*>(cw + ((lane >> 3) + 8 * u) * 32 + (lane & 7) * 4) = v;
+            }
+            CSEG_WAVE_LOCKSTEP();
+            float bv[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) bv[r] = cw[(8 * (r >> 2) + 4 * h + (r & 3)) * 32 + r32];
+            CSEG_WAVE_LOCKSTEP();                      // the next feature tile's stores must not overtake these reads
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(hv[r], bv[r], acc[t], 0, 0, 0);
+        }
+    }
+    // acc[t] layout: col = d0 + t*32 + (lane&31), rows I0 + (r&3) + 8*(r>>2) + 4*h
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int t = 0; t < BW_DT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float* p = &red[(r & 3) + 8 * (r >> 2) + 4 * h][t * 32 + r32];
+                    *p = (w == 0) ? acc[t][r] : *p + acc[t][r];
+                }
+        }
+        __syncthreads();
+    }
+    const float scale = d_loss[0] * inv_tau;
+    for (int e = threadIdx.x; e < 32 * BW_DT * 32; e += 256) {
+        const int rr = e / (BW_DT * 32), cc = e - rr * (BW_DT * 32);
+        const int ii = I0 + rr, dd = d0 + cc;
+        if (ii < Ncap && dd < D) parts[((size_t)split * Ncap + ii) * D + dd] = ii < N ? red[rr][cc] * scale : 0.f;
+    }
+}
+
+// scatter_dn_kernel with the number of parts of the bank-mode backward, bwd_splits(N, M, D)
+__global__ __launch_bounds__(256) void scatter_dn_bank_kernel(const float* __restrict__ parts, const int32_t* __restrict__ sel_pix,
+                                                              const int32_t* __restrict__ header, int Ncap, int M, int B, int D, int P,
+                                                              float scale, float* __restrict__ d_embed) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int N = device_n(header, Ncap);
+    if (r >= N) return;
+    const int n_parts = bwd_splits(N, M, D);
+    const int bp = sel_pix[r];
+    if (bp < 0 || bp >= B * P) return;
+    const int b = bp / P, pix = bp - b * P;
+    float* dst = d_embed + (size_t)b * D * P + pix;
+    for (int d = lane; d < D; d += 64) {
+        float acc = 0.f;
+        for (int s = 0; s < n_parts; ++s) acc += parts[((size_t)s * Ncap + r) * D + d];
+        dst[(size_t)d * P] = acc * scale;
+    }
+}
+
+// the ColSrc of the memory bank for the device-N entry points (what make_col builds from a descriptor in mode 2)
+int make_bank_col(const float* segq, const float* pixq, int bank_classes, int bank_size, int Ncap, int D, ColSrc* c) {
+    CSEG_REQUIRE(segq && pixq && bank_classes > 0 && bank_size > 0, "contrast (device N, bank): needs both queues");
+    CSEG_REQUIRE(Ncap > 0 && D > 0, "contrast (device N, bank): empty problem");
+    CSEG_REQUIRE(D % 8 == 0, "contrast: D=%d must be a multiple of 8", D);
+    CSEG_REQUIRE((size_t)bank_classes * 2 * bank_size < ((size_t)1 << 31), "contrast (device N, bank): K*2*ms overflows int32");
+    c->mode = 2;
+    c->D = D;
+    c->M = bank_classes * 2 * bank_size;
+    c->rows = nullptr; c->labs = nullptr;
+    c->segq = segq; c->pixq = pixq; c->ms = bank_size;
+    c->packed = (bank_classes - 1) * 2 * bank_size;
+    // N <= Ncap is all the host knows: the reference's self mask needs N <= M (loss_contrast_mem.py:134-138)
+    CSEG_REQUIRE(Ncap <= c->M, "contrast (device N, bank): Ncap=%d anchors > M=%d contrast columns", Ncap, c->M);
+    return 1;
+}
+
 }  // namespace
 
 extern "C" int cseg_gather_anchors_dn(const float* embed, int B, int D, int P, const int32_t* part_idx, const int32_t* sel_pos,
@@ -947,6 +1159,62 @@ extern "C" int cseg_contrast_bwd_dn(const float* anchors, const int32_t* a_lab, 
     hipLaunchKernelGGL(bwd_dn_kernel, grid, dim3(256), 0, (hipStream_t)stream_, S_ws, round32(Ncap), anchors, a_lab, header, Ncap, D,
                        row_stats, d_loss, 1.0f / temperature, nDt, d_anchor_parts);
     CSEG_CHECK_LAUNCH("bwd_dn_kernel");
+    return 1;
+}
+
+extern "C" int cseg_contrast_bwd_parts_cap_bank(int Ncap, int M, int D) {
+    int cap = 1;
+    for (int n = 1; n <= Ncap; ++n) {
+        const int s = bwd_splits(n, M, D);
+        if (s > cap) cap = s;
+    }
+    return cap;
+}
+
+extern "C" int cseg_contrast_fwd_dn_bank(const float* anchors, const int32_t* a_lab, const int32_t* header, int Ncap, int D,
+                                         const float* segment_queue, const float* pixel_queue, int bank_classes, int bank_size,
+                                         float temperature, float base_temperature, float* S_ws, float* row_stats, float* row_loss,
+                                         float* loss, cseg_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    ColSrc col;
+    if (!make_bank_col(segment_queue, pixel_queue, bank_classes, bank_size, Ncap, D, &col)) return 0;
+    CSEG_REQUIRE(temperature > 0.f && base_temperature > 0.f, "contrast: temperatures must be > 0");
+    const int ldS = round32(col.M);
+    const int nIb = (Ncap + SG_T - 1) / SG_T, nJb = (col.M + SG_T - 1) / SG_T;
+    hipLaunchKernelGGL(s_gemm_dn_bank_kernel, dim3(nIb * nJb), dim3(256), 0, stream, anchors, header, Ncap, col, 1.0f / temperature,
+                       S_ws, ldS, nJb);
+    CSEG_CHECK_LAUNCH("s_gemm_dn_bank_kernel");
+    hipLaunchKernelGGL(row_pass_dn_bank_kernel, dim3(Ncap), dim3(256), 0, stream, S_ws, ldS, header, col, a_lab,
+                       temperature / base_temperature, row_stats, row_loss);
+    CSEG_CHECK_LAUNCH("row_pass_dn_bank_kernel");
+    hipLaunchKernelGGL(mean_dn_kernel, dim3(1), dim3(256), 0, stream, row_loss, header, Ncap, loss);
+    CSEG_CHECK_LAUNCH("mean_dn_kernel");
+    return 1;
+}
+
+extern "C" int cseg_contrast_bwd_dn_bank(const float* anchors, const int32_t* a_lab, const int32_t* header, int Ncap, int D,
+                                         const float* segment_queue, const float* pixel_queue, int bank_classes, int bank_size,
+                                         float temperature, const float* S_ws, const float* row_stats, const float* d_loss,
+                                         float* d_anchor_parts, cseg_stream_t stream_) {
+    (void)anchors;                                   // (the bank gets no gradient and the anchors are not a contrast column)
+    ColSrc col;
+    if (!make_bank_col(segment_queue, pixel_queue, bank_classes, bank_size, Ncap, D, &col)) return 0;
+    CSEG_REQUIRE(temperature > 0.f, "contrast backward (device N, bank): temperature must be > 0");
+    const int nI = (Ncap + 31) / 32, nDt = (D + BW_DT * 32 - 1) / (BW_DT * 32);
+    dim3 grid(nI * nDt, cseg_contrast_bwd_parts_cap_bank(Ncap, col.M, D));
+    hipLaunchKernelGGL(bwd_dn_bank_kernel, grid, dim3(256), 0, (hipStream_t)stream_, S_ws, round32(col.M), header, Ncap, col, a_lab,
+                       row_stats, d_loss, 1.0f / temperature, nDt, d_anchor_parts);
+    CSEG_CHECK_LAUNCH("bwd_dn_bank_kernel");
+    return 1;
+}
+
+extern "C" int cseg_scatter_anchor_grad_dn_bank(const float* d_anchor_parts, const int32_t* sel_pix, const int32_t* header, int Ncap,
+                                                int M, int B, int D, int P, float scale, float* d_embed, cseg_stream_t stream_) {
+    CSEG_REQUIRE(Ncap > 0 && M > 0 && B > 0 && D > 0 && P > 0 && (size_t)B * P < ((size_t)1 << 31),
+                 "scatter_anchor_grad_dn_bank: bad shape");
+    hipLaunchKernelGGL(scatter_dn_bank_kernel, dim3((Ncap + 3) / 4), dim3(256), 0, (hipStream_t)stream_, d_anchor_parts, sel_pix,
+                       header, Ncap, M, B, D, P, scale, d_embed);
+    CSEG_CHECK_LAUNCH("scatter_dn_bank_kernel");
     return 1;
 }
 

@@ -13,11 +13,11 @@
 //
 // Everything is integer arithmetic: under the same seed the picks are those of the host path bit for bit.
 #include "cseg_common.h"
+#include "cseg_sampling.h"
 
 namespace {
 
 constexpr int MT_N = 624, MT_M = 397;
-constexpr int SP_THREADS = 256;
 
 __device__ __forceinline__ uint32_t mt_twist(uint32_t u, uint32_t v) {
     return (((u & 0x80000000u) | (v & 0x7fffffffu)) >> 1) ^ ((v & 1u) ? 0x9908b0dfu : 0u);
@@ -81,23 +81,6 @@ __global__ __launch_bounds__(SP_THREADS) void mt_kernel(uint32_t* __restrict__ s
     if (tid == 0) state[MT_N] = (uint32_t)pos;
 }
 
-// exclusive prefix sum over the block of one value per thread (thread order); *sum = the block's total
-__device__ __forceinline__ int block_excl_scan(int v, int* red, int tid, int* sum) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const int inc = wave_incl_scan_i(v, lane);
-    __syncthreads();
-    if (lane == 63) red[wave] = inc;
-    __syncthreads();
-    int base = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < SP_THREADS / 64; ++w) {
-        if (w < wave) base += red[w];
-        all += red[w];
-    }
-    *sum = all;
-    return base + inc - v;
-}
-
 // lib/loss/anchor_sampling.py:keep_rule (loss_contrast.py:66-77) in integers: x >= n_view / 2  <=>  2 x >= n_view. false = fell through.
 __device__ __forceinline__ bool keep_rule(int nh, int ne, int n_view, int* kh, int* ke) {
     const bool h_ok = 2 * (long)nh >= n_view, e_ok = 2 * (long)ne >= n_view;
@@ -117,8 +100,6 @@ __device__ __forceinline__ bool keep_rule(int nh, int ne, int n_view, int* kh, i
     }
     return true;
 }
-
-__device__ __forceinline__ int draws_of(int n) { return n > 0 ? n - 1 : 0; }
 
 // seg_plan [B*K][2]: rank a of the segment among the qualifying ones (-1: does not qualify), offset of its first draw.
 __global__ __launch_bounds__(SP_THREADS) void plan_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ mine_status,

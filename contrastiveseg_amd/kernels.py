@@ -426,6 +426,71 @@ class PixelContrastDevice(Function):
         return (d_embed,) + (None,) * 7
 
 
+# "1" / "0" overrides the config key contrast.device_bank of the memory-bank criteria (anchor sampling AND the enqueue on the device,
+# DESIGN.md section 23); unset = the config decides (default off).
+DEVICE_BANK = os.environ.get("CSEG_DEVICE_BANK")
+
+
+class PixelContrastDeviceBank(Function):
+    """PixelContrastDevice against the memory bank (mode 2, three-launch forward): N = header[0] in device memory only, the queues read
+    in place, M = K * 2 * ms. Keeps the version guard of the host path (the bank must not change between forward and backward) and the
+    SparseGradSlot deposit ([Ncap, D] rows, rows >= N exactly zero)."""
+
+    @staticmethod
+    def forward(ctx, embed, part_idx, sel_pos, a_lab, header, temperature, base_temperature, segment_queue, pixel_queue, slot=None):
+        if not embed.is_contiguous():
+            embed = embed.contiguous()
+        B, D = embed.shape[:2]
+        P = embed.shape[2] * embed.shape[3]
+        Ncap = sel_pos.numel()
+        Kc, ms, Dq = segment_queue.shape
+        if Dq != D or tuple(pixel_queue.shape) != (Kc, ms, Dq):
+            raise RuntimeError("queue shapes %s / %s do not match D=%d" % (tuple(segment_queue.shape), tuple(pixel_queue.shape), D))
+        M = Kc * 2 * ms
+        dev = embed.device
+        lib = _hip.lib()
+        anchors = torch.empty(Ncap, D, dtype=F32, device=dev)
+        sel_pix = torch.empty(Ncap, dtype=I32, device=dev)
+        _hip.call("cseg_gather_anchors_dn", _p(embed, F32, "embed"), B, D, P, _p(part_idx, I32, "part_idx"), _p(sel_pos, I32, "sel_pos"),
+                  _p(header, I32, "header"), Ncap, _pf(anchors), _pf(sel_pix), _hip.stream_ptr())
+        S = torch.empty(lib.cseg_contrast_ws_bytes(Ncap, M) // 4, dtype=F32, device=dev)
+        row_stats = torch.empty(Ncap, 4, dtype=F32, device=dev)
+        row_loss = torch.empty(Ncap, dtype=F32, device=dev)
+        loss = torch.empty(1, dtype=F32, device=dev)
+        _hip.call("cseg_contrast_fwd_dn_bank", _pf(anchors), _p(a_lab, I32, "a_lab"), _p(header, I32, "header"), Ncap, D,
+                  _p(segment_queue, F32, "segment_queue"), _p(pixel_queue, F32, "pixel_queue"), Kc, ms, float(temperature),
+                  float(base_temperature), _pf(S), _pf(row_stats), _pf(row_loss), _pf(loss), _hip.stream_ptr())
+        ctx.saved = (anchors, a_lab, header, S, row_stats, sel_pix, segment_queue, pixel_queue)
+        ctx.bank_versions = _bank_versions(segment_queue, pixel_queue)
+        ctx.temperature = float(temperature)
+        ctx.slot = slot
+        ctx.embed_shape = embed.shape
+        ctx.mark_non_differentiable(sel_pix)
+        return loss.reshape(()), sel_pix
+
+    @staticmethod
+    def backward(ctx, g, _g_sel):
+        B, D, h, w = ctx.embed_shape
+        anchors, a_lab, header, S, row_stats, sel_pix, segment_queue, pixel_queue = ctx.saved
+        _check_bank_unchanged(ctx.bank_versions, segment_queue, pixel_queue)
+        dev = sel_pix.device
+        Ncap = sel_pix.numel()
+        Kc, ms, _ = segment_queue.shape
+        M = Kc * 2 * ms
+        n_parts = _hip.lib().cseg_contrast_bwd_parts_cap_bank(Ncap, M, D)
+        parts = torch.empty(n_parts, Ncap, D, dtype=F32, device=dev)
+        d_loss = g.reshape(1).to(F32).contiguous()
+        _hip.call("cseg_contrast_bwd_dn_bank", _pf(anchors), _pf(a_lab), _pf(header), Ncap, D, _pf(segment_queue), _pf(pixel_queue), Kc, ms,
+                  ctx.temperature, _pf(S), _pf(row_stats), _p(d_loss, F32, "d_loss"), _pf(parts), _hip.stream_ptr())
+        if ctx.slot is not None:
+            rows = parts.sum(0) if n_parts > 1 else parts[0]
+            return (ctx.slot.deposit(rows, sel_pix.clamp_min(0), ctx.embed_shape),) + (None,) * 9
+        d_embed = torch.zeros(B, D, h, w, dtype=F32, device=dev)
+        _hip.call("cseg_scatter_anchor_grad_dn_bank", _pf(parts), _pf(sel_pix), _pf(header), Ncap, M, B, D, h * w, 1.0, _pf(d_embed),
+                  _hip.stream_ptr())
+        return (d_embed,) + (None,) * 9
+
+
 # ----------------------------------------------------------------------------------------------------------
 # HRNet head: upsample + concat
 # ----------------------------------------------------------------------------------------------------------
@@ -1025,6 +1090,31 @@ def queue_write_pixels(keys, src_img, src_pos, dst_cls, dst_row, pixel_queue):
               _p(src_pos, I32, "src_pos"), _p(dst_cls, I32, "dst_cls"), _p(dst_row, I32, "dst_row"),
               src_img.numel(), _p(pixel_queue, F32, "pixel_queue"), ms, _hip.stream_ptr())
     torch.autograd.graph.increment_version(pixel_queue)
+
+
+@torch.no_grad()
+def queue_enqueue_device(keys, labels, stride, segment_queue, segment_queue_ptr, pixel_queue, pixel_queue_ptr, pixel_update_freq,
+                         rng_state):
+    """Trainer._dequeue_and_enqueue (reference trainer_contrastive.py:102-138) as one call that reads nothing back: counts, class
+    sums, pointer arithmetic, the torch.randperm replicas (from `rng_state`, i32 [625], advanced in place), last-writer-wins and both
+    row writers on the device (contrast.device_bank). All four queue tensors are updated in place."""
+    B, D = keys.shape[:2]
+    Pk = keys.shape[2] * keys.shape[3]
+    _, H, W = labels.shape
+    Kc, ms, _ = segment_queue.shape
+    dev = keys.device
+    n_ws = _hip.lib().cseg_queue_enqueue_ws_ints(B, Kc, H, W, int(stride), int(pixel_update_freq))
+    if n_ws == 0:
+        raise RuntimeError("queue_enqueue_device: bad shape (B=%d, K=%d, labels %dx%d, stride %s, pixel_update_freq %s)"
+                           % (B, Kc, H, W, stride, pixel_update_freq))
+    ws = torch.empty(n_ws, dtype=I32, device=dev)
+    sums = torch.empty(B, Kc, D, dtype=F32, device=dev)
+    _hip.call("cseg_queue_enqueue_device", _p(keys, F32, "keys"), _p(labels, I64, "labels"), B, D, Pk, H, W, int(stride), Kc, ms,
+              int(pixel_update_freq), _p(segment_queue, F32, "segment_queue"), _p(segment_queue_ptr, I64, "segment_queue_ptr"),
+              _p(pixel_queue, F32, "pixel_queue"), _p(pixel_queue_ptr, I64, "pixel_queue_ptr"), _p(rng_state, I32, "rng_state"),
+              _pf(sums), _pf(ws), _hip.stream_ptr())
+    for t in (segment_queue, segment_queue_ptr, pixel_queue, pixel_queue_ptr):
+        torch.autograd.graph.increment_version(t)              # written through raw pointers
 
 
 # ----------------------------------------------------------------------------------------------------------

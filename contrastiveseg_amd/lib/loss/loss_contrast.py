@@ -28,7 +28,10 @@ bank, as the reference does; `cross_rank` does not apply to it.
 `contrast.device_sampling` (opt-in, CSEG_DEVICE_SAMPLING=0|1 overrides): the keep rule and the torch.randperm
 replicas run on the device too (csrc/sampling.hip), from a device copy of the CPU generator's mt19937 state, and the gather / contrast /
 scatter kernels read the number of anchors from device memory. No device-to-host copy, no data-dependent host value, so the criterion
-can be captured in a hipGraph; same picks, loss and gradient as the host path under the same seed."""
+can be captured in a hipGraph; same picks, loss and gradient as the host path under the same seed.
+
+`contrast.device_bank` (opt-in, CSEG_DEVICE_BANK=0|1 overrides): the same for the memory-bank criteria, together with
+the enqueue of Trainer._dequeue_and_enqueue -- both draw from the criterion's one device generator, in the reference's order."""
 from abc import ABC
 
 import numpy as np
@@ -78,6 +81,21 @@ def device_sampling_wanted(configer):
     return want
 
 
+def device_bank_wanted(configer):
+    """contrast.device_bank (bool, default false), overridden by CSEG_DEVICE_BANK=0|1. Read by the memory-bank criteria only."""
+    want = bool(configer.get('contrast', 'device_bank')) if configer.exists('contrast', 'device_bank') else False
+    env = getattr(K, "DEVICE_BANK", None)
+    if env in ("0", "1"):
+        want = env == "1"
+    return want
+
+
+def _refuse_device_bank_multi_rank():
+    if D.get_world_size() > 1 or D.exercise_single_rank():
+        raise NotImplementedError("contrast.device_bank on more than one rank (or under CSEG_DIST_SINGLE_RANK=1) is a follow-up: the "
+                                  "multi-rank enqueue (Trainer._enqueue_global) plans the global batch on the host")
+
+
 def _grad_slot(embed):
     """kernels.SparseGradSlot the projection head attached to the embedding it produced (row-sparse backward, opt-in:
     lib/models/modules/projection.py), or None = the dense zero-filled gradient."""
@@ -117,7 +135,11 @@ class PixelContrastLoss(nn.Module, ABC):
         self._side = None            # side HIP stream for mining (created lazily on the first GPU call)
         self.last_selection = None   # {'sel_pix': i32 [N] (b*P+pixel, view-major), 'plan': SelectionPlan}
         self.device_sampling = device_sampling_wanted(configer)
-        if self.device_sampling and self.uses_memory_bank:
+        # memory-bank criteria: anchor sampling AND Trainer._dequeue_and_enqueue on the device, one generator stream
+        self.device_bank = self.uses_memory_bank and device_bank_wanted(configer)
+        if self.device_bank:
+            self._check_device_bank()
+        if self.device_sampling and self.uses_memory_bank and not self.device_bank:
             # follow-up: the enqueue draws of Trainer._dequeue_and_enqueue come from the same CPU generator stream; one stream split over
             # two generators would silently leave the reference's index sequence
             raise NotImplementedError("contrast.device_sampling is not available for the memory-bank criteria (their enqueue draws "
@@ -125,6 +147,21 @@ class PixelContrastLoss(nn.Module, ABC):
         # plain attributes, not buffers: state_dict keys stay those of the reference
         self._rng_state = None       # i32 [625] on the device: mt19937 words + pos, imported from torch's CPU generator on first use
         self.sampling_sticky = None  # i32 [1] on the device: OR of the status bits of every step (Trainer._display reads it)
+
+    def _check_device_bank(self):
+        """What the device route of the memory-bank criteria cannot do, refused when the criterion is built."""
+        c = self.configer
+        _refuse_device_bank_multi_rank()
+        ms = c.get('contrast', 'memory_size') if c.exists('contrast', 'memory_size') else None
+        freq = c.get('contrast', 'pixel_update_freq') if c.exists('contrast', 'pixel_update_freq') else None
+        if ms is not None and freq is not None and freq > ms:
+            # the reference's `[-K:]` write fails there; the device writers would have to invent a rule
+            raise ValueError("contrast.device_bank: pixel_update_freq=%d is larger than memory_size=%d" % (freq, ms))
+        num_classes = c.get('data', 'num_classes') if c.exists('data', 'num_classes') else None
+        if ms is not None and num_classes is not None and self.max_samples > num_classes * 2 * ms:
+            # the kernels need N <= M (the reference's self mask, loss_contrast_mem.py:134-138) and N is not known on the host
+            raise ValueError("contrast.device_bank: max_samples=%d is larger than the bank's num_classes * 2 * memory_size = %d columns"
+                             % (self.max_samples, num_classes * 2 * ms))
 
     # -- mining ------------------------------------------------------------------------------------------
     def _classify(self, feats, labels, predict, seg, prezeroed=False):
@@ -210,9 +247,9 @@ class PixelContrastLoss(nn.Module, ABC):
         if self._rng_state is not None:
             _host.mt_import(self._rng_state.cpu().numpy().view(np.uint32))
 
-    def _forward_device(self, feats, labels, predict, seg, seg_ready):
+    def _forward_device(self, feats, labels, predict, seg, seg_ready, segment_queue=None, pixel_queue=None):
         """Mining, selection, gather, contrast: all enqueued, nothing read back. Mining and planning keep the side-stream fork and
-        join of _mine when the model recorded `seg_ready`."""
+        join of _mine when the model recorded `seg_ready`. With the two queues the contrast set is the memory bank, read in place."""
         rng = self._rng_on(feats.device)
 
         def run():
@@ -223,8 +260,13 @@ class PixelContrastLoss(nn.Module, ABC):
             (part_idx, sel_pos, a_lab, header), _ = self._fork_join(seg_ready, seg, labels, run)
         else:
             (part_idx, sel_pos, a_lab, header), _ = run()
-        loss, sel_pix = K.PixelContrastDevice.apply(feats, part_idx, sel_pos, a_lab, header, self.temperature,
-                                                    self.base_temperature, _grad_slot(feats))
+        if segment_queue is not None:
+            loss, sel_pix = K.PixelContrastDeviceBank.apply(feats, part_idx, sel_pos, a_lab, header, self.temperature,
+                                                            self.base_temperature, segment_queue.contiguous(), pixel_queue.contiguous(),
+                                                            _grad_slot(feats))
+        else:
+            loss, sel_pix = K.PixelContrastDevice.apply(feats, part_idx, sel_pos, a_lab, header, self.temperature,
+                                                        self.base_temperature, _grad_slot(feats))
         self.last_selection = {"sel_pix": sel_pix, "header": header, "plan": None}
         return loss
 
@@ -237,6 +279,11 @@ class PixelContrastLoss(nn.Module, ABC):
         assert labels is not None and (predict is not None or seg is not None)
         world = D.get_world_size()
         cross = segment_queue is None and (world > 1 or D.exercise_single_rank()) and self.cross_rank
+        if self.device_bank:
+            # (also without the queues -- the bank-free term of a memory criterion: the enqueue draws from the device generator, and one
+            # stream split over two generators would leave the reference's index sequence)
+            _refuse_device_bank_multi_rank()
+            return self._forward_device(feats, labels, predict, seg, seg_ready, segment_queue, pixel_queue)
         if self.device_sampling:
             if cross:
                 raise NotImplementedError("contrast.device_sampling with contrast.cross_rank on more than one rank (or under "

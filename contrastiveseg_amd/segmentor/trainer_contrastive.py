@@ -8,7 +8,7 @@ What changes underneath (MI355X-first):
     the CPU randperm stream needs) instead of O(100) implicit syncs of the reference's Python loops;
   * `_dequeue_and_enqueue` is one histogram + one all-class reduction + two row writers on the device; pointer
     arithmetic, last-writer-wins resolution and the CPU `torch.randperm` draws (same order as the reference) stay
-    on the host;
+    on the host (with `contrast.device_bank` they move to the device too: cseg_queue_enqueue_device);
   * data: any iterable yielding {'img', 'labelmap'} dicts; by default a seeded synthetic loader resident in HBM
     (file datasets / cv2 augmentation are out of scope)."""
 import os
@@ -148,6 +148,14 @@ class Trainer(object):
     def _dequeue_and_enqueue(self, keys, labels, segment_queue, segment_queue_ptr, pixel_queue, pixel_queue_ptr):
         """reference :102-138; all four queue tensors are updated in place. Multi-rank runs: _enqueue_global (the same update from
         the GLOBAL batch on every rank)."""
+        bank = self._device_bank_criterion()
+        if bank is not None:
+            # contrast.device_bank: planner, draws (the criterion's device generator) and writers in one call, nothing read back
+            if get_world_size() > 1 or exercise_single_rank():
+                raise NotImplementedError("contrast.device_bank on more than one rank (or under CSEG_DIST_SINGLE_RANK=1) is a follow-up: "
+                                          "_enqueue_global plans the global batch on the host")
+            return K.queue_enqueue_device(keys.contiguous(), labels.contiguous(), self.network_stride, segment_queue, segment_queue_ptr,
+                                          pixel_queue, pixel_queue_ptr, self.pixel_update_freq, bank._rng_on(keys.device))
         if get_world_size() > 1 or exercise_single_rank():
             return self._enqueue_global(keys, labels, segment_queue, segment_queue_ptr, pixel_queue, pixel_queue_ptr)
         Kc = segment_queue.shape[0]
@@ -171,6 +179,16 @@ class Trainer(object):
                                  r[:, 3].contiguous(), pixel_queue)
         segment_queue_ptr.copy_(torch.from_numpy(seg_ptr.astype(np.int64)))
         pixel_queue_ptr.copy_(torch.from_numpy(pix_ptr.astype(np.int64)))
+
+    def _device_bank_criterion(self):
+        """The memory-bank contrast criterion whose contrast.device_bank is on (it owns the device generator), or None."""
+        loss = getattr(self, 'pixel_loss', None)
+        if loss is None:
+            return None
+        for m in loss.modules():
+            if getattr(m, 'device_bank', False):
+                return m
+        return None
 
     def _enqueue_global(self, keys, labels, segment_queue, segment_queue_ptr, pixel_queue, pixel_queue_ptr):
         """The memory bank under data parallelism (exchange 4). The reference lets every rank enqueue its own

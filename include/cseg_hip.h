@@ -157,6 +157,21 @@ int cseg_contrast_bwd_dn(const float* anchors, const int32_t* a_lab, const int32
 int cseg_scatter_anchor_grad_dn(const float* d_anchor_parts, const int32_t* sel_pix, const int32_t* header, int Ncap, int B, int D,
                                 int P, float scale, float* d_embed, cseg_stream_t stream);
 
+/* The same in bank mode (contrast.device_bank): mode 2 of cseg_contrast_fwd / cseg_contrast_bwd (three-launch forward) with N = header[0]
+ * read on the device. The queues [K,ms,D] are read in place, M = K*2*ms; Ncap <= M is required. S_ws cseg_contrast_ws_bytes(Ncap, M)
+ * bytes (row stride round32(M)), d_anchor_parts [cseg_contrast_bwd_parts_cap_bank(Ncap, M, D), Ncap, D] with rows >= N and splits >=
+ * cseg_contrast_bwd_parts(N, M, D) zero; the scatter sums the first cseg_contrast_bwd_parts(N, M, D) parts. N = 0: loss NaN. */
+int cseg_contrast_fwd_dn_bank(const float* anchors, const int32_t* a_lab, const int32_t* header, int Ncap, int D,
+                              const float* segment_queue, const float* pixel_queue, int bank_classes, int bank_size, float temperature,
+                              float base_temperature, float* S_ws, float* row_stats, float* row_loss, float* loss, cseg_stream_t stream);
+int cseg_contrast_bwd_parts_cap_bank(int Ncap, int M, int D);
+int cseg_contrast_bwd_dn_bank(const float* anchors, const int32_t* a_lab, const int32_t* header, int Ncap, int D,
+                              const float* segment_queue, const float* pixel_queue, int bank_classes, int bank_size, float temperature,
+                              const float* S_ws, const float* row_stats, const float* d_loss, float* d_anchor_parts,
+                              cseg_stream_t stream);
+int cseg_scatter_anchor_grad_dn_bank(const float* d_anchor_parts, const int32_t* sel_pix, const int32_t* header, int Ncap, int M, int B,
+                                     int D, int P, float scale, float* d_embed, cseg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * HRNet head input: bilinear(align_corners=True) upsample of the low-resolution maps to the first map's size
  * fused with the channel concat.  Replaces lib/models/nets/hrnet.py:86-91 (3x F.interpolate + torch.cat).
@@ -238,6 +253,17 @@ int cseg_queue_write_segments(const float* sums, const int32_t* counts, const in
 int cseg_queue_write_pixels(const float* keys, int B, int D, int Pk, const int32_t* src_img,
                             const int32_t* src_pos, const int32_t* dst_cls, const int32_t* dst_row, int n_rows,
                             float* pixel_queue, int ms, cseg_stream_t stream);
+
+/* The whole update on the device (contrast.device_bank): counts, class sums, the walk over the (image, class >= 1) pairs with the
+ * reference's pointer arithmetic, one torch.randperm replica per pair from rng_state (the mt19937 state of cseg_sample_anchors,
+ * advanced in place by sum max(n - 1, 0) draws), last-writer-wins resolution and both row writers. Nothing is read back.
+ *   segment_queue_ptr, pixel_queue_ptr [K] i64, updated in place; sums [B,K,D] f32 workspace;
+ *   ws [cseg_queue_enqueue_ws_ints(B, K, H, W, stride, pixel_update_freq)] i32 workspace (0 = bad arguments).
+ * Needs K >= 2, 1 <= pixel_update_freq <= ms and ceil(H/stride)*ceil(W/stride) <= Pk. No hipMemsetAsync is issued. */
+size_t cseg_queue_enqueue_ws_ints(int B, int K, int H, int W, int stride, int pixel_update_freq);
+int cseg_queue_enqueue_device(const float* keys, const int64_t* labels, int B, int D, int Pk, int H, int W, int stride, int K, int ms,
+                              int pixel_update_freq, float* segment_queue, int64_t* segment_queue_ptr, float* pixel_queue,
+                              int64_t* pixel_queue_ptr, uint32_t* rng_state, float* sums, int32_t* ws, cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused (Sync)BatchNorm + residual add + ReLU, NCHW fp32.  Replaces what
