@@ -186,6 +186,12 @@ SIGNATURES = {
     "cseg_lovasz_grad": (_c_int, [_ptr, _ptr, _c_int, _c_int] + [_ptr] * 6),
     "cseg_lovasz_finish": (_c_int, [_ptr, _ptr, _c_int, _c_int] + [_ptr] * 4),
     "cseg_lovasz_bwd": (_c_int, [_ptr] * 5 + [_c_int] * 6 + [_ptr] * 3),
+    "cseg_ohem_sel_ints": (_c_int, []),
+    "cseg_ohem_reduce_blocks": (_c_int, [ctypes.c_long]),
+    "cseg_ohem_prob": (_c_int, [_ptr, _ptr] + [_c_int] * 7 + [_c_float] + [_ptr] * 6),
+    "cseg_ohem_select": (_c_int, [_ptr, ctypes.c_long, _c_float, _c_int, _c_int, _c_int, _ptr, _ptr]),
+    "cseg_ohem_reduce": (_c_int, [_ptr] * 4 + [_c_int, ctypes.c_long] + [_ptr] * 6),
+    "cseg_ohem_bwd": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 7 + [_ptr] * 7),
     "cseg_conv_stat_segments":(ctypes.c_size_t, [_c_int] * 4),
     "cseg_conv3x3_split_fwd_st": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 7 + [_ptr, _ptr, _ptr, _ptr, _ptr]),
     "cseg_conv1x1_split_fwd_st": (_c_int, [_ptr, _ptr, _ptr] + [_c_int] * 5 + [_ptr, _ptr, _ptr, _ptr, _ptr]),

@@ -993,6 +993,137 @@ def lovasz_softmax(seg, target, want_terms=False, ignore_index=-1, status=None):
 
 
 # ----------------------------------------------------------------------------------------------------------
+# segmentation term: upsample + cross entropy with online hard example mining (csrc/ohem.hip)
+# ----------------------------------------------------------------------------------------------------------
+OHEM_SENTINEL = 2.0      # p at a pixel whose label is not in [0, K): above every probability, never selected, never kept
+_OHEM_STATE = 3 * 1024   # sel = three histograms of 1024 bins, then the state words {#{p < thresh}, n, k, prefix, rank, done, kth, thr}
+
+
+def _ohem_shapes(what, seg, target):
+    if seg.dim() != 4 or target.dim() != 3 or target.shape[0] != seg.shape[0]:
+        raise RuntimeError("%s: seg %s / target %s, expected [B,K,h,w] / [B,H,W]" % (what, tuple(seg.shape), tuple(target.shape)))
+    B, K, h, w = seg.shape
+    _, H, W = target.shape
+    if B * H * W >= 2 ** 31:
+        raise RuntimeError("%s: %d label pixels (P = B * H * W must be below 2^31)" % (what, B * H * W))
+    if H < h or W < w:
+        raise RuntimeError("%s: only upsampling is supported (%dx%d -> %dx%d)" % (what, h, w, H, W))
+    return B, K, h, w, H, W, B * H * W
+
+
+def _ohem_sel(dev):
+    return torch.empty(_hip.lib().cseg_ohem_sel_ints(), dtype=I32, device=dev)
+
+
+def _ohem_prob(seg, target, ignore_index, thresh, status, want_lse):
+    B, K, h, w, H, W, P = _ohem_shapes("ohem_prob", seg, target)
+    seg, target = seg.contiguous(), target.contiguous()
+    dev = seg.device
+    p, nll = torch.empty(B, H, W, dtype=F32, device=dev), torch.empty(B, H, W, dtype=F32, device=dev)
+    lse = torch.empty(B, H, W, dtype=F32, device=dev) if want_lse else None
+    sel = _ohem_sel(dev)
+    _hip.call("cseg_ohem_prob", _p(seg, F32, "seg"), _p(target, I64, "target"), int(ignore_index), B, K, h, w, H, W, float(thresh), _pf(p),
+              _pf(nll), _pf(lse) if lse is not None else _null(), _pf(sel), _p(status, I32, "status") if status is not None else _null(),
+              _hip.stream_ptr())
+    return p, nll, lse, sel
+
+
+@torch.no_grad()
+def ohem_prob(seg, target, ignore_index=-1, status=None):
+    """seg [B,K,h,w] f32 (coarse logits), target [B,H,W] i64 -> p, nll, lse, each [B,H,W] f32, of the bilinear(align_corners=True)
+    upsampling of seg, which is never built: p = softmax(logits)[label], nll = lse - logit_label. At a pixel whose label is not in [0, K)
+    p = OHEM_SENTINEL and nll = 0; labels that are neither `ignore_index` nor a class id are also counted in status[1] (i32 [4])."""
+    p, nll, lse, _ = _ohem_prob(seg, target, ignore_index, 0.0, status, True)
+    return p, nll, lse
+
+
+@torch.no_grad()
+def ohem_threshold(p, thresh, min_kept, shortcut=True):
+    """p f32 (any shape; values above 1 mark invalid pixels) -> device scalars (thr f32, k i32, n_valid i32): n_valid = #{p <= 1},
+    k = min(max(1, min_kept), n_valid - 1), thr = max(element of 0-based rank k of the valid p in ascending order, fp32(thresh)).
+    `shortcut`: thr = thresh without the refinement passes when #{p < thresh} >= k + 1 (the same bits either way). Nothing is read
+    back. n_valid == 0: k = 0 and thr = thresh."""
+    if p.numel() < 1 or p.numel() >= 2 ** 31:
+        raise RuntimeError("ohem_threshold: %d pixels (1 <= P < 2^31)" % p.numel())
+    p = p.contiguous()
+    sel = _ohem_sel(p.device)
+    _hip.call("cseg_ohem_select", _p(p, F32, "p"), p.numel(), float(thresh), int(min_kept), int(bool(shortcut)), 0, _pf(sel),
+              _hip.stream_ptr())
+    st = sel[_OHEM_STATE:]
+    return st[7:8].view(F32)[0].clone(), st[2].clone(), st[1].clone()
+
+
+def _ohem_reduce(p, nll, target, weight, K, sel):
+    P = p.numel()
+    dev = p.device
+    nb = _hip.lib().cseg_ohem_reduce_blocks(P)
+    partial = torch.empty(nb, dtype=F64, device=dev)
+    pcount = torch.empty(nb, dtype=I32, device=dev)
+    out = torch.empty(4, dtype=F32, device=dev)
+    outi = torch.empty(4, dtype=I32, device=dev)
+    _hip.call("cseg_ohem_reduce", _pf(p), _pf(nll), _p(target, I64, "target"), _p(weight, F32, "ce_weight") if weight is not None else _null(),
+              int(K), P, _pf(sel), _pf(partial), _pf(pcount), _pf(out), _pf(outi), _hip.stream_ptr())
+    return out, outi
+
+
+@torch.no_grad()
+def ohem_reduce(p, nll, target, thr, weight=None, num_classes=None):
+    """The reduction stage alone, for tests: p, nll [B,H,W] f32, thr a device f32 scalar -> out f32 [4] {loss, kept, thr, 0} and
+    outi i32 [4] {kept, ...}: the mean over the COUNT of the pixels with p < thr of weight[label] * nll (NaN when there is none)."""
+    sel = torch.zeros(_hip.lib().cseg_ohem_sel_ints(), dtype=I32, device=p.device)
+    sel[_OHEM_STATE + 7:_OHEM_STATE + 8] = thr.reshape(1).to(F32).view(I32)
+    if weight is not None and num_classes is None:
+        num_classes = weight.numel()
+    return _ohem_reduce(p.contiguous(), nll.contiguous(), target.contiguous(), weight, num_classes or 1, sel)
+
+
+class OhemCE(Function):
+    """FSOhemCELoss(F.interpolate(seg, target.shape, bilinear, align_corners=True), target) of the reference
+    (lib/loss/loss_helper.py:215-261) without the [B,K,H,W] tensor, the sort and the host round trips: probabilities + level-0 histogram,
+    radix select of the rank-k probability, thresholded reduction (csrc/ohem.hip). Saved for the backward: seg, target, p, lse [B,H,W],
+    out and its integer companion; nll is forward-only and lse is not written without a gradient to compute."""
+
+    @staticmethod
+    def forward(ctx, seg, target, weight, ignore_index, thresh, min_kept, status, want_grad):
+        B, K, h, w, H, W, P = _ohem_shapes("ohem_ce", seg, target)
+        seg, target = seg.contiguous(), target.contiguous()
+        p, nll, lse, sel = _ohem_prob(seg, target, ignore_index, thresh, status, want_grad)
+        _hip.call("cseg_ohem_select", _pf(p), P, float(thresh), int(min_kept), 1, 1, _pf(sel), _hip.stream_ptr())
+        out, outi = _ohem_reduce(p, nll, target, weight, K, sel)
+        if want_grad:
+            ctx.save_for_backward(seg, target, p, lse, out, outi)
+        ctx.weight = weight
+        ctx.ignore_index = int(ignore_index)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_out):
+        seg, target, p, lse, out, outi = ctx.saved_tensors
+        B, K, h, w = seg.shape
+        _, H, W = target.shape
+        d_seg = torch.empty_like(seg)
+        g = g.reshape(1).to(F32).contiguous()
+        wp = _p(ctx.weight, F32, "ce_weight") if ctx.weight is not None else _null()
+        _hip.call("cseg_ohem_bwd", _p(seg, F32, "seg"), _p(target, I64, "target"), wp, ctx.ignore_index, B, K, h, w, H, W, _pf(p), _pf(lse),
+                  _pf(out), _pf(outi), _p(g, F32, "d_loss"), _pf(d_seg), _hip.stream_ptr())
+        return d_seg, None, None, None, None, None, None, None
+
+
+def ohem_ce(seg, target, weight=None, ignore_index=-1, thresh=0.7, min_kept=1, status=None, want_terms=False):
+    """The OHEM cross entropy on coarse or label-resolution logits -> the 0-d loss; with want_terms also the f32 [4] device tensor
+    {loss, kept pixels, thr, valid pixels}. min_kept goes through max(1, .) as in the reference. The kept set is p < thr, strict: the
+    rank-k pixel and everything tied with it are not kept. No kept pixel (every valid pixel at or above thr, or no valid pixel): the loss
+    is NaN -- the reference's value in the first case; in the second it raises IndexError, which needs a host synchronisation -- and the
+    gradient is all zeros. Labels that are neither `ignore_index` nor in [0, K) are dropped and counted in status[1] (i32 [4],
+    optional). No host synchronisation; works under torch.no_grad()."""
+    loss, out = OhemCE.apply(seg, target, weight, ignore_index, thresh, max(1, int(min_kept)), status,
+                             torch.is_grad_enabled() and seg.requires_grad)
+    return (loss, out) if want_terms else loss
+
+
+# ----------------------------------------------------------------------------------------------------------
 # test phase: multi-scale + flip fusion with the argmax, confusion matrix (csrc/ms_eval.hip)
 # ----------------------------------------------------------------------------------------------------------
 MS_MAX_TERMS = 8

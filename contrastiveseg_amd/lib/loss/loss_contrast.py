@@ -41,8 +41,8 @@ import torch.nn as nn
 from contrastiveseg_amd import _host
 from contrastiveseg_amd import kernels as K
 from contrastiveseg_amd.lib.loss.anchor_sampling import plan_selection
-from contrastiveseg_amd.lib.loss.loss_helper import (FSAuxCELOVASZLoss, FSAuxCELoss, FSAuxRMILoss, FSCELOVASZLoss, FSCELoss,
-                                                     FSRMILoss)
+from contrastiveseg_amd.lib.loss.loss_helper import (FSAuxCELOVASZLoss, FSAuxCELoss, FSAuxOhemCELoss, FSAuxRMILoss, FSCELOVASZLoss,
+                                                     FSCELoss, FSOhemCELoss, FSRMILoss)
 from contrastiveseg_amd.lib.utils import distributed as D
 from contrastiveseg_amd.lib.utils.tools.logger import Logger as Log
 
@@ -361,13 +361,18 @@ class PixelContrastLoss(nn.Module, ABC):
 # the segmentation criterion of the composite criteria: [takes the auxiliary map too][term]. 'rmi' without an auxiliary map: the
 # reference constructs FSAuxRMILoss there and unpacks the single logit tensor as a pair, which cannot run; FSRMILoss is what it sets
 # out to be
-SEG_CRITERIA = {False: {"ce": FSCELoss, "rmi": FSRMILoss, "lovasz": FSCELOVASZLoss},
-                True: {"ce": FSAuxCELoss, "rmi": FSAuxRMILoss, "lovasz": FSAuxCELOVASZLoss}}
+SEG_CRITERIA = {False: {"ce": FSCELoss, "rmi": FSRMILoss, "lovasz": FSCELOVASZLoss, "ohem": FSOhemCELoss},
+                True: {"ce": FSAuxCELoss, "rmi": FSAuxRMILoss, "lovasz": FSAuxCELOVASZLoss, "ohem": FSAuxOhemCELoss}}
 
 
 class _ContrastComposite(nn.Module, ABC):
     """seg_criterion(seg | [seg_aux, seg]) + loss_weight * contrast_criterion(embed): the four registered contrast criteria (this
-    module and loss_contrast_mem.py) are this class with other data."""
+    module and loss_contrast_mem.py) are this class with other data.
+
+    `contrast.use_ohem` (bool, default false; all four criteria) gives the segmentation term hard-pixel mining: FSOhemCELoss on the
+    segmentation map (FSAuxOhemCELoss with an auxiliary map), with loss.params.ohem_thresh / ohem_minkeep. The switch is the project's own,
+    like FSAuxCELOVASZLoss: the reference reaches its OHEM criteria only through the fs_ohemce_loss / fs_auxohemce_loss keys, never from
+    a contrast criterion. Together with use_rmi or use_lovasz it is refused: each of the three replaces the same term."""
     aux = False                          # the segmentation criterion takes [seg_aux, seg]
     contrast_class = PixelContrastLoss   # the memory pair: loss_contrast_mem.PixelContrastLoss
     reads_lovasz = False                 # the memory pair reads contrast.use_lovasz too (the reference's bank-free pair has no such switch)
@@ -390,6 +395,13 @@ class _ContrastComposite(nn.Module, ABC):
                                           "switch one of them off")
             if self.use_lovasz:
                 term = "lovasz"
+        self.use_ohem = bool(self.configer.get('contrast', 'use_ohem')) if self.configer.exists('contrast', 'use_ohem') else False
+        if self.use_ohem:
+            for other in ("use_rmi", "use_lovasz"):
+                if getattr(self, other, False):
+                    raise NotImplementedError("contrast.use_ohem together with contrast.%s: both replace the segmentation term; "
+                                              "switch one of them off" % other)
+            term = "ohem"
         self.seg_criterion = SEG_CRITERIA[self.aux][term](configer=configer)
         self.contrast_criterion = self.contrast_class(configer=configer)
 

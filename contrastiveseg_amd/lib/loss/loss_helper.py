@@ -97,6 +97,32 @@ class FSCELOVASZLoss(nn.Module):
         return self.ce_loss(inputs, targets[0]) + K.lovasz_softmax(inputs, targets[0], ignore_index=self.ignore_index)
 
 
+class FSOhemCELoss(FSCELoss):
+    """Cross entropy over the hard pixels only (reference :215-261): among the valid pixels, those whose probability of the true class
+    lies below max(ohem_thresh, the probability of rank min(ohem_minkeep, n - 1) in ascending order), averaged over their count (not over
+    the sum of ce_weight as FSCELoss). Computed by the kernels of csrc/ohem.hip on the coarse logits. The reference's constructor contract:
+    loss.params.ohem_thresh and ohem_minkeep are required, max(1, ohem_minkeep) is applied, ce_weight / ce_reduction / ce_ignore_index as
+    FSCELoss (the mean reduction only). Takes the segmentation map or the trainer's dict with 'seg'. When no pixel is kept the loss is NaN
+    (kernels.ohem_ce). An FSCELoss, so that bad_label_count / bad_label_total see its `status`."""
+
+    def __init__(self, configer=None):
+        super(FSOhemCELoss, self).__init__(configer)
+        params = configer.get("loss", "params") if configer.exists("loss", "params") else {}
+        for key in ("ohem_thresh", "ohem_minkeep"):
+            if key not in params:
+                raise KeyError("FSOhemCELoss: loss.params.%s is required" % key)
+        self.thresh = float(params["ohem_thresh"])
+        self.min_kept = max(1, int(params["ohem_minkeep"]))
+
+    def _one(self, inp, target):
+        return K.ohem_ce(inp, target, self.weight, self.ignore_index, self.thresh, self.min_kept, self.status)
+
+    def forward(self, inputs, *targets, **kwargs):
+        if isinstance(inputs, dict) and "seg" in inputs:
+            inputs = inputs["seg"]
+        return super(FSOhemCELoss, self).forward(inputs, *targets, **kwargs)
+
+
 class _FSAuxLoss(nn.Module):
     """term(seg) * w_seg + ce(aux) * w_aux (reference :301-329): `ce_loss` always takes the auxiliary map; the sub-module `seg_name`
     takes the segmentation map -- `ce_loss` again, or an instance of `seg_class` built next to it."""
@@ -132,6 +158,11 @@ class FSAuxCELOVASZLoss(_FSAuxLoss):
     Lovasz criterion for the contrast losses is FSCELOVASZLoss in the registered memory criterion; this is the project's own composite
     for mem_contrast_auxce_loss (the DeepLab / OCR memory models, whose auxiliary map gets the plain CE as everywhere else)."""
     seg_name, seg_class = "lovasz_loss", FSCELOVASZLoss
+
+
+class FSAuxOhemCELoss(_FSAuxLoss):
+    """ohem(seg) * w_seg + ce(aux) * w_aux (reference :264-298): plain CE on the auxiliary map, hard-pixel mining on the segmentation map."""
+    seg_name, seg_class = "ohem_ce_loss", FSOhemCELoss
 
 
 def bad_label_total(criterion, device=None):

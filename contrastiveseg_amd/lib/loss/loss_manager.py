@@ -1,14 +1,17 @@
 """Loss registry with the reference's keys (lib/loss/loss_manager.py:27-68). Only the criteria of the contrastive
-hot path are registered; every other key of the reference's table is out of scope."""
+hot path and the OHEM cross entropy of its HRNet-OCR recipes (fs_ohemce_loss / fs_auxohemce_loss) are registered;
+every other key of the reference's table is out of scope."""
 from contrastiveseg_amd.lib.loss.loss_contrast import ContrastAuxCELoss, ContrastCELoss
 from contrastiveseg_amd.lib.loss.loss_contrast_mem import ContrastAuxCELoss as MemContrastAuxCELoss
 from contrastiveseg_amd.lib.loss.loss_contrast_mem import ContrastCELoss as MemContrastCELoss
-from contrastiveseg_amd.lib.loss.loss_helper import FSAuxCELoss, FSCELoss
+from contrastiveseg_amd.lib.loss.loss_helper import FSAuxCELoss, FSAuxOhemCELoss, FSCELoss, FSOhemCELoss
 from contrastiveseg_amd.lib.utils.tools.logger import Logger as Log
 
 SEG_LOSS_DICT = {
     'fs_ce_loss': FSCELoss,
     'fs_auxce_loss': FSAuxCELoss,
+    'fs_ohemce_loss': FSOhemCELoss,
+    'fs_auxohemce_loss': FSAuxOhemCELoss,
     'contrast_auxce_loss': ContrastAuxCELoss,
     'contrast_ce_loss': ContrastCELoss,
     'mem_contrast_ce_loss': MemContrastCELoss,

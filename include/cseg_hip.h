@@ -821,6 +821,39 @@ int cseg_lovasz_finish(const double* partial, const int32_t* gtot, int K, int P,
 int cseg_lovasz_bwd(const float* seg, const int64_t* target, const float* gbuf, const double* outd, const float* d_loss, int B, int K,
                     int h, int w, int H, int W, float* stats, float* d_seg, cseg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Cross entropy with online hard example mining (csrc/ohem.hip).  Replaces FSOhemCELoss (lib/loss/loss_helper.py:215-261) on
+ * F.interpolate(seg, (H, W), bilinear, align_corners=True): with p = softmax(logits)[label] at the n valid pixels (0 <= label < K),
+ * k = min(max(1, min_kept), n - 1) and kth = the element of 0-based rank k of p ascending, thr = max(kth, fp32 thresh), the kept pixels
+ * are those with p < thr (strict) and the loss is the mean over their COUNT of w_label * (lse - logit_label).  A k-th-smallest selection
+ * (radix select over the bit pattern of p, three levels of 1024 bins), not a sort; nothing is read back, integer atomics only.
+ * P = B * H * W < 2^31, H >= h, W >= w, at most 17 label pixels per coarse cell.
+ *
+ *   cseg_ohem_sel_ints  size of `sel` (i32: three histograms + state words; zero-filled by the entry points themselves, by a kernel).
+ *   cseg_ohem_prob      -> p, nll = lse - logit_label, lse (or NULL) [B,H,W] f32; p = 2 and nll = 0 at invalid pixels; the level-0
+ *                       histogram and #{p < thresh} into sel; status (or NULL): status[1] += labels neither ignore_label nor in [0, K).
+ *   cseg_ohem_select    the stored p [P] -> n, k, kth, thr in sel.  have_level0: sel comes from cseg_ohem_prob of the same p and thresh
+ *                       (otherwise the level-0 pass runs here).  shortcut: #{p < thresh} >= k + 1 gives thr = thresh without a refinement
+ *                       pass; thr is bit-identical with and without it (kth is then not computed and reported as 0).
+ *   cseg_ohem_reduce    partial [cseg_ohem_reduce_blocks(P)] f64 and pcount [same] i32 scratch; target is read only with weight.
+ *                       -> out [4] f32 {loss, kept, thr, n} and outi [4] i32 {kept, n, k, shortcut taken}.  kept == 0 (every valid pixel at
+ *                       or above thr, or n == 0): loss = NaN, as the reference's mean of an empty selection (for n == 0 the reference
+ *                       raises IndexError, which would need a synchronisation here).
+ *   cseg_ohem_bwd       d_seg [B,K,h,w] = [p < thr] w_label (softmax - onehot) d_loss / kept through the bilinear adjoint; all zeros when
+ *                       kept == 0.  Reads the stored p, lse, out, outi; no atomics: deterministic.
+ * ------------------------------------------------------------------------------------------------ */
+int cseg_ohem_sel_ints(void);
+int cseg_ohem_reduce_blocks(long P);
+int cseg_ohem_prob(const float* seg, const int64_t* target, int ignore_label, int B, int K, int h, int w, int H, int W, float thresh,
+                   float* p, float* nll, float* lse, int32_t* sel, int32_t* status, cseg_stream_t stream);
+int cseg_ohem_select(const float* p, long P, float thresh, int min_kept, int shortcut, int have_level0, int32_t* sel,
+                     cseg_stream_t stream);
+int cseg_ohem_reduce(const float* p, const float* nll, const int64_t* target, const float* weight, int K, long P, const int32_t* sel,
+                     double* partial, int32_t* pcount, float* out, int32_t* outi, cseg_stream_t stream);
+int cseg_ohem_bwd(const float* seg, const int64_t* target, const float* weight, int ignore_label, int B, int K, int h, int w, int H,
+                  int W, const float* p, const float* lse, const float* out, const int32_t* outi, const float* d_loss, float* d_seg,
+                  cseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
