@@ -173,6 +173,8 @@ SIGNATURES = {
     "cseg_ms_fuse_argmax": (_c_int, [_c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int), ctypes.POINTER(_c_int),
                                      ctypes.POINTER(_c_float)] + [_c_int] * 4 + [_ptr, _ptr, _ptr]),
     "cseg_confusion_update": (_c_int, [_ptr, _ptr, ctypes.c_long, _c_int, _c_int, _ptr, _ptr]),
+    "cseg_crop_fuse_argmax": (_c_int, [_c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int)] + [_c_int] * 4 +
+                              [_ptr, _ptr, _ptr]),
     "cseg_rmi_pool_blocks": (_c_int, [_c_int] * 4),
     "cseg_rmi_pool_fwd": (_c_int, [_ptr, _ptr] + [_c_int] * 10 + [_ptr] * 5),
     "cseg_rmi_cov": (_c_int, [_ptr, _ptr] + [_c_int] * 4 + [_ptr, _ptr, _ptr]),

@@ -1164,6 +1164,73 @@ def ms_fuse_argmax(terms, H, W, want_fused=False, want_pred=True):
     return (pred, fused) if want_fused else pred
 
 
+CROP_TERM_INTS = 7        # CSEG_CROP_TERM_INTS
+
+
+def crop_tiles(total, crop):
+    """Number of tiles along one axis of a canvas: len(_decide_intersection(total, crop)) of the reference's tester."""
+    return -(-int(total) // int(crop))
+
+
+@torch.no_grad()
+def crop_fuse_argmax(terms, H, W, want_fused=False, want_pred=True):
+    """segmentor/tester.py:351-378, 505-523 (sscrop_test / mscrop_test) + the argmax of :189 without the logits canvas, the count
+    canvas or any [B,K,H,W] tensor (csrc/crop_eval.hip). `terms`, in scale_search order, holds
+      (plain, flipped)                 a plain term as in ms_fuse_argmax with weight 1: coarse logits [B,K,h,w] of the whole input at
+                                       one scale, and of the mirrored input;
+      (plain, flipped, canvas, crop)   a tiled term: canvas = (hs, ws), crop = (ch, cw), plain = the stacked coarse crop maps
+                                       [ny*nx, B, K, hc, wc] in the reference's tile order (height-major; ny = crop_tiles(hs, ch), nx =
+                                       crop_tiles(ws, cw)), flipped = the same stack for the mirrored input, whose tiles cover the
+                                       mirrored canvas.
+    One of plain / flipped may be None. -> pred u8 [B,H,W] (first index among equal maxima), or (pred, fused) with the fp32 [B,K,H,W]
+    sum when want_fused; pred is None when want_pred is False."""
+    n = len(terms)
+    if n < 1 or n > MS_MAX_TERMS:
+        raise RuntimeError("crop_fuse_argmax: %d terms (1 to %d are supported)" % (n, MS_MAX_TERMS))
+    keep, pa, pb = [], (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
+    dims = (ctypes.c_int * (CROP_TERM_INTS * n))()
+    B = K = dev = None
+    for i, term in enumerate(terms):
+        if len(term) not in (2, 4):
+            raise RuntimeError("crop_fuse_argmax: term %d has %d entries, expected (plain, flipped) or (plain, flipped, canvas, crop)"
+                               % (i, len(term)))
+        a, b = term[0], term[1]
+        tiled = len(term) == 4
+        first = a if a is not None else b
+        if first is None:
+            raise RuntimeError("crop_fuse_argmax: term %d has neither a plain nor a flipped map" % i)
+        if B is None:
+            B, K = first.shape[1:3] if tiled else first.shape[:2]
+            dev = first.device
+        want = "[tiles, %d, %d, hc, wc]" % (B, K) if tiled else "[%d, %d, h, w]" % (B, K)
+        if first.dim() != (5 if tiled else 4) or tuple(first.shape[-4:-2]) != (B, K):
+            raise RuntimeError("crop_fuse_argmax: term %d is %s, expected %s" % (i, tuple(first.shape), want))
+        if a is not None and b is not None and b.shape != a.shape:
+            raise RuntimeError("crop_fuse_argmax: the flipped %s of term %d is %s, its plain one %s"
+                               % ("stack" if tiled else "map", i, tuple(b.shape), tuple(a.shape)))
+        d = [0, 0, 0, 0, first.shape[-2], first.shape[-1], 1]
+        if tiled:
+            (hs, ws), (ch, cw) = term[2], term[3]
+            d[:4] = [int(hs), int(ws), int(ch), int(cw)]
+            d[6] = first.shape[0]
+            if min(d[:4]) > 0 and (hs < ch or ws < cw):
+                raise RuntimeError("crop_fuse_argmax: term %d: the canvas %d x %d is smaller than the crop %d x %d" % (i, hs, ws, ch, cw))
+            if min(d[:4]) > 0 and d[6] != crop_tiles(hs, ch) * crop_tiles(ws, cw):
+                raise RuntimeError("crop_fuse_argmax: term %d: a stack of %d tiles for the %d x %d tiles of a %d x %d canvas under a "
+                                   "%d x %d crop" % (i, d[6], crop_tiles(hs, ch), crop_tiles(ws, cw), hs, ws, ch, cw))
+        dims[CROP_TERM_INTS * i:CROP_TERM_INTS * (i + 1)] = d
+        for t, arr, what in ((a, pa, "plain"), (b, pb, "flipped")):
+            if t is not None:
+                t = t.contiguous()
+                arr[i] = _p(t, F32, what + (" stack" if tiled else " map")).value
+                keep.append(t)
+    pred = torch.empty(B, int(H), int(W), dtype=U8, device=dev) if want_pred else None
+    fused = torch.empty(B, K, int(H), int(W), dtype=F32, device=dev) if want_fused else None
+    _hip.call("cseg_crop_fuse_argmax", n, pa, pb, dims, B, K, int(H), int(W), _pf(pred) if want_pred else _null(),
+              _pf(fused) if want_fused else _null(), _hip.stream_ptr())
+    return (pred, fused) if want_fused else pred
+
+
 @torch.no_grad()
 def confusion_update(pred, target, confusion, ignore_index=-1):
     """confusion [K,K] i64 (rows = ground truth, columns = prediction) += RunningScore._fast_hist(target, pred, K) with

@@ -1,6 +1,6 @@
-"""Test phase with the reference's surface (segmentor/tester.py:56-398: `Tester(configer).test()`, `ss_test`, `ms_test`) and
-config keys (test.mode, test.scale_search, optional test.scale_weights, test.batch_size, test.out_dir, test.save_prob,
-network.resume).
+"""Test phase with the reference's surface (segmentor/tester.py:56-523: `Tester(configer).test()`, `ss_test`, `ms_test`, `sscrop_test`,
+`mscrop_test`) and config keys (test.mode, test.scale_search, optional test.scale_weights, test.crop_size, test.batch_size,
+test.out_dir, test.save_prob, network.resume).
 
 What the reference does per scale -- upsample two coarse logit maps to the input size, flip one, add, scale, accumulate into a
 [B,K,H,W] tensor (:310-327, :380-398), then move everything to the host for the argmax (:169-189) -- is linear up to the argmax.
@@ -8,7 +8,11 @@ Here the model runs once per scale and once more on the mirrored input, only the
 kernels.ms_fuse_argmax call per batch writes the prediction as one byte per pixel; the fused fp32 map exists only under
 test.save_prob. Scoring (where ground truth exists) is kernels.confusion_update into an on-device RunningScore.
 
-Outside the accelerated path, refused by name: sscrop_test, mscrop_test, ms_test_depth, crf_ss_test, the offset path, and every
+The sliding-crop modes (:351-378, :505-523) build a logits canvas and a count canvas of [B,K,H*scale,W*scale] per scale and flip. Here
+the resized input is cut into the reference's tiles, the model runs once per tile, its coarse output goes into a preallocated stack
+[tiles,B,K,hc,wc], and one kernels.crop_fuse_argmax call per batch does the rest: no canvas exists.
+
+Outside the accelerated path, refused by name: ms_test_depth, crf_ss_test, the offset path, and every
 data_transformer for which the reference's final cv2.resize(..., INTER_CUBIC) to the original size (:180-181) would not be the
 identity (anything but size_mode fix_size + align_method only_pad, the pair the loader implements). The colour `vis/` output is
 not written."""
@@ -24,8 +28,9 @@ from contrastiveseg_amd.lib.metrics.running_score import RunningScore
 from contrastiveseg_amd.lib.utils.distributed import get_rank
 from contrastiveseg_amd.lib.utils.tools.logger import Logger as Log
 
-SUPPORTED_MODES = ('ss_test', 'ms_test')
-REFUSED_MODES = ('sscrop_test', 'mscrop_test', 'ms_test_depth', 'crf_ss_test')
+SUPPORTED_MODES = ('ss_test', 'ms_test', 'sscrop_test', 'mscrop_test')
+CROP_MODES = ('sscrop_test', 'mscrop_test')
+REFUSED_MODES = ('ms_test_depth', 'crf_ss_test')
 
 
 def check_config(configer):
@@ -40,9 +45,10 @@ def check_config(configer):
                                       .format(mode, SUPPORTED_MODES))
         raise NotImplementedError('test.mode {!r} is not a test mode; supported: {}'.format(mode, SUPPORTED_MODES))
     scales, weights = [1.0], None
-    if mode == 'ms_test':
+    if mode in ('ms_test', 'mscrop_test'):
         scales = list(configer.get('test', 'scale_search')) if configer.exists('test', 'scale_search') else [1.0]
-        if configer.exists('test', 'scale_weights') and configer.get('test', 'scale_weights') is not None:
+        # (mscrop_test takes no weights: reference :511-522)
+        if mode == 'ms_test' and configer.exists('test', 'scale_weights') and configer.get('test', 'scale_weights') is not None:
             weights = list(configer.get('test', 'scale_weights'))
             if len(weights) != len(scales):
                 raise ValueError('test.scale_weights has {} entries for the {} scales of test.scale_search'
@@ -55,6 +61,37 @@ def check_config(configer):
             raise NotImplementedError('test.data_transformer {}: only size_mode fix_size + align_method only_pad is implemented (the '
                                       'final resize to the original size is the identity there; it is not approximated)'.format(dt))
     return mode, scales, weights
+
+
+def tile_starts(total, crop):
+    """Tile starts along one axis, the reference's _decide_intersection (:525-533) with its stride = the crop length:
+    min(i * crop, total - crop) for i < ceil(total / crop). Every index is covered by one or two tiles."""
+    if crop < 1 or total < crop:
+        raise ValueError('a canvas of {} cannot be tiled with crops of {}'.format(total, crop))
+    return [min(i * crop, total - crop) for i in range(K.crop_tiles(total, crop))]
+
+
+def resolve_crop_size(configer, mode):
+    """test.crop_size = [crop_h, crop_w] of the sliding-crop modes (crop_size[0] is the height, as the reference indexes it), or None
+    for the other modes."""
+    if mode not in CROP_MODES:
+        return None
+    crop = configer.get('test', 'crop_size') if configer.exists('test', 'crop_size') else None
+    if crop is None:
+        raise NotImplementedError('test.mode {!r} needs test.crop_size = [crop_h, crop_w]; it is not set'.format(mode))
+    if not isinstance(crop, (list, tuple)) or len(crop) != 2 or not all(isinstance(c, int) and c > 0 for c in crop):
+        raise ValueError('test.crop_size {!r}: expected two positive integers [crop_h, crop_w]'.format(crop))
+    return int(crop[0]), int(crop[1])
+
+
+def check_canvas(input_size, crop, scale):
+    """-> the canvas (int(H * scale), int(W * scale)) of one sliding-crop scale; ValueError when a crop does not fit into it (the
+    reference runs into an IndexError there)."""
+    hs, ws = int(input_size[0] * scale), int(input_size[1] * scale)
+    if hs < crop[0] or ws < crop[1]:
+        raise ValueError('scale {}: the canvas {} x {} of a {} x {} input is smaller than the crop {} x {}'
+                         .format(scale, hs, ws, input_size[0], input_size[1], crop[0], crop[1]))
+    return hs, ws
 
 
 def dataset_id_lut(configer):
@@ -81,6 +118,9 @@ class Tester(object):
     def __init__(self, configer, seg_net=None, test_loader=None):
         self.configer = configer
         self.mode, self.scales, self.weights = check_config(configer)
+        self.crop_size = resolve_crop_size(configer, self.mode)
+        if self.mode == 'mscrop_test' and configer.exists('test', 'scale_weights') and configer.get('test', 'scale_weights') is not None:
+            Log.warn('test.scale_weights is ignored in mscrop_test, as in the reference')
         from contrastiveseg_amd.lib.models.model_manager import ModelManager
         from contrastiveseg_amd.segmentor.tools.module_runner import ModuleRunner
         self.module_runner = ModuleRunner(configer)
@@ -139,6 +179,61 @@ class Tester(object):
             terms.append((a, b, 1.0 if self.weights is None else self.weights[i]))
         return self._fuse(terms, inputs, want_fused)
 
+    def _crop_stack(self, scaled, crop):
+        """The coarse outputs of the net on the reference's tiles of `scaled`, height-major (:364-373) -> [ny*nx,B,K,hc,wc]."""
+        ch, cw = crop
+        stack, t = None, 0
+        ys, xs = tile_starts(scaled.shape[2], ch), tile_starts(scaled.shape[3], cw)
+        for y0 in ys:
+            for x0 in xs:
+                out = self._coarse(scaled[:, :, y0:y0 + ch, x0:x0 + cw].contiguous())
+                if stack is None:
+                    stack = torch.empty((len(ys) * len(xs),) + tuple(out.shape), dtype=out.dtype, device=out.device)
+                stack[t].copy_(out)
+                t += 1
+        return stack
+
+    def _crop_term(self, inputs, mirrored, crop, scale):
+        """One scale of mscrop_test (:511-522): a plain term below 1, a tiled term from 1 on; mirrored=None leaves the flip out."""
+        if scale < 1:
+            return (self._coarse(self._scaled(inputs, scale)), None if mirrored is None else self._coarse(self._scaled(mirrored, scale)))
+        canvas = check_canvas(inputs.shape[-2:], crop, scale)
+        return (self._crop_stack(self._scaled(inputs, scale), crop),
+                None if mirrored is None else self._crop_stack(self._scaled(mirrored, scale), crop), canvas, crop)
+
+    @torch.no_grad()
+    def sscrop_test(self, inputs, crop_size, scale=1, want_fused=False):
+        """reference :351-378 + the argmax: -> pred u8 [B,H,W], or (pred, fused) when want_fused. As in the reference, the scale is
+        taken as a sliding-crop scale whatever its value."""
+        self.seg_net.eval()
+        crop = (int(crop_size[0]), int(crop_size[1]))
+        canvas = check_canvas(inputs.shape[-2:], crop, scale)
+        h, w = inputs.shape[-2:]
+        return K.crop_fuse_argmax([(self._crop_stack(self._scaled(inputs, scale), crop), None, canvas, crop)], h, w, want_fused=want_fused)
+
+    @torch.no_grad()
+    def mscrop_test(self, inputs, crop_size, want_fused=False, flip=True):
+        """reference :505-523 + the argmax: per scale of test.scale_search ss_test below 1 and sscrop_test from 1 on, each once more on
+        the mirrored input; test.scale_weights plays no part. Only coarse maps are kept."""
+        self.seg_net.eval()
+        crop = (int(crop_size[0]), int(crop_size[1]))
+        for scale in self.scales:          # before the first forward pass
+            if scale >= 1:
+                check_canvas(inputs.shape[-2:], crop, scale)
+        mirrored = torch.flip(inputs, dims=[3]) if flip else None
+        terms = [self._crop_term(inputs, mirrored, crop, scale) for scale in self.scales]
+        h, w = inputs.shape[-2:]
+        return K.crop_fuse_argmax(terms, h, w, want_fused=want_fused)
+
+    def _predict(self, inputs):
+        if self.mode == 'ms_test':
+            return self.ms_test(inputs, self.save_prob)
+        if self.mode == 'sscrop_test':
+            return self.sscrop_test(inputs, self.crop_size, 1, self.save_prob)
+        if self.mode == 'mscrop_test':
+            return self.mscrop_test(inputs, self.crop_size, self.save_prob)
+        return self.ss_test(inputs, 1, self.save_prob)
+
     # ------------------------------------------------------------------------------------------------------
     def _loader(self):
         if self.test_loader is None:
@@ -165,7 +260,7 @@ class Tester(object):
             inputs = batch['img']
             if inputs.device != self.device:
                 inputs = inputs.to(self.device, non_blocking=True)
-            out = self.ms_test(inputs, self.save_prob) if self.mode == 'ms_test' else self.ss_test(inputs, 1, self.save_prob)
+            out = self._predict(inputs)
             pred, fused = out if self.save_prob else (out, None)
             labels = batch.get('labelmap')
             if labels is not None:

@@ -758,6 +758,31 @@ int cseg_confusion_update(const uint8_t* pred, const int64_t* target, long N, in
                           cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Test phase, sliding crops (csrc/crop_eval.hip).  Replaces the tensor work of segmentor/tester.py:351-378, 505-523 (sscrop_test /
+ * mscrop_test) with the argmax of :189.  Neither the [B,K,hs,ws] logits canvas nor the count canvas nor a [B,K,H,W] tensor is needed.
+ *
+ * n_terms terms (1..8) in scale_search order; all arrays are HOST arrays, copied into the kernel's argument block.  Per term
+ * CSEG_CROP_TERM_INTS ints in `dims`: {hs, ws, ch, cw, hc, wc, n_tiles}.
+ *   tiled term   canvas hs x ws = (int(H*scale), int(W*scale)), crop ch x cw (ch is the height), coarse map of one crop hc x wc.
+ *                plain[i]: device pointer to [ny*nx, B, K, hc, wc] f32, the net's coarse logits of every tile in the reference's tile
+ *                order (height-major), ny = ceil(hs/ch), nx = ceil(ws/cw); the tile starts are computed in the kernel as
+ *                start(i) = min(i * crop, total - crop) (_decide_intersection of :525-533).  n_tiles must be ny*nx; the canvas must
+ *                not be smaller than the crop.  flipped[i]: the same stack for the horizontally mirrored input (it tiles the MIRRORED
+ *                canvas), or NULL.
+ *   plain term   hs = ws = ch = cw = 0: plain[i] / flipped[i] are [B,K,hc,wc] maps as in cseg_ms_fuse_argmax (weight 1), n_tiles is
+ *                ignored.
+ * One of plain[i], flipped[i] may be NULL, not both (`plain` or `flipped` itself may be NULL as well).
+ * Per output pixel and class:  v = 0;  v = v + (S(plain[i])[y,x] + S(flipped[i])[y,W-1-x]),  S = the canvas (the sum of the tiles'
+ * maps, each upsampled to the crop, in tile order, divided by the number of covering tiles: 1, 2 or 4, exact) resized to H x W; both
+ * resizes are bilinear(align_corners=True) with torch's fp32 source index.  A canvas tap whose blend factor is exactly 0 is not read.
+ *   pred  [B,H,W] u8, first index among equal maxima, or NULL;  fused [B,K,H,W] f32 (the value v), or NULL; not both NULL.
+ * K <= 256; every stack has fewer than 2^30 elements.  Deterministic (no atomics).
+ * ------------------------------------------------------------------------------------------------ */
+#define CSEG_CROP_TERM_INTS 7
+int cseg_crop_fuse_argmax(int n_terms, const float* const* plain, const float* const* flipped, const int* dims, int B, int K, int H,
+                          int W, uint8_t* pred, float* fused, cseg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Region mutual information segmentation term (csrc/rmi.hip).  Replaces lib/loss/rmi_loss.py:283-402 (RMILoss.forward_sigmoid ->
  * rmi_lower_bound) applied to F.interpolate(seg, (H, W), bilinear, align_corners=True); no [B,K,H,W] tensor is needed.
  * Only rmi_radius 3, rmi_pool_way 0 (max pooling), rmi_pool_size = rmi_pool_stride = 3 (every *_RMI.json of the reference); the pooled
