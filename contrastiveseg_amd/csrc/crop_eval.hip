@@ -19,10 +19,10 @@
 //
 // crop_fuse_kernel   a block owns an 8 x 32 patch of output pixels. All tap data depend on y alone or on x alone: per term the block
 //                    computes them once for its 8 rows, 32 columns and 32 mirrored columns into LDS (tile starts from (hs, ws, ch, cw)
-//                    inside the kernel: start(i) = min(i * crop, total - crop)), with the package's fp32 index arithmetic (ac_scale,
-//                    bl_tap) on both levels. Classes run in the outer loop, terms inside. Floating-point contraction is off, every
+//                    inside the kernel: start(i) = min(i * crop, total - crop)), with the package's fp32 index arithmetic (bl_tap;
+//                    DESIGN.md section 26) on both levels. Classes run in the outer loop, terms inside. Floating-point contraction is off, every
 //                    rounding is where the source puts it. No atomics: deterministic.
-#include "cseg_bilinear.h"
+#include "cseg_taps.h"
 
 #pragma clang fp contract(off)
 

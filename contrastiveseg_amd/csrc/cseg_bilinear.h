@@ -8,25 +8,7 @@
 // element is read from HBM once per band (halo rows of neighbouring bands are the only re-reads).
 // Gather kernel (fallback when a band does not fit in LDS): one thread per coarse element walks its footprint.
 #pragma once
-#include "cseg_common.h"
-
-__device__ __forceinline__ void bl_tap(float s, int n_in, int o, int& i0, int& i1, float& l1) {
-    const float f = s * (float)o;
-    i0 = (int)f;
-    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    l1 = f - (float)i0;
-}
-
-// first / last fine index whose lower tap i0 lies in [c_lo - 1, c_hi]  (c_lo..c_hi coarse indices, inclusive)
-__device__ __forceinline__ void bl_fine_range(float s, int n_fine, int c_lo, int c_hi, int& lo, int& hi) {
-    lo = 0; hi = n_fine - 1;
-    if (s > 0.f) {
-        lo = max(0, (int)ceilf((float)(c_lo - 1) / s) - 1);
-        while (lo < n_fine - 1 && (int)(s * (float)lo) < c_lo - 1) ++lo;
-        hi = min(n_fine - 1, (int)floorf((float)(c_hi + 1) / s) + 1);
-        while (hi > 0 && (int)(s * (float)hi) > c_hi) --hi;
-    }
-}
+#include "cseg_taps.h"
 
 constexpr int BL_MAX_TAPS = 40;   // fine columns touching one coarse column (2/scale + 1) -- up to 16x upsampling
 constexpr int BL_TY = 4;          // coarse rows per block (larger bands measured slower: fewer, LDS-heavier blocks)
@@ -88,8 +70,7 @@ __global__ __launch_bounds__(256) void bilinear_adjoint_band_kernel(const float*
             if (t < nt) {
                 int x0, x1; float l1;
                 bl_tap(sx, ws, x_lo + t, x0, x1, l1);
-                if (x0 == xs) wv += 1.f - l1;
-                if (x1 == xs) wv += l1;
+                wv = bl_adjoint_weight(x0, x1, l1, xs);
             }
             wx[t] = wv;
         }
@@ -111,9 +92,7 @@ __global__ __launch_bounds__(256) void bilinear_adjoint_band_kernel(const float*
         for (int fy = 0; fy < nY; ++fy) {
             int y0, y1; float l1;
             bl_tap(sy, hs, Y_lo + fy, y0, y1, l1);
-            float wy = 0.f;
-            if (y0 == ys) wy += 1.f - l1;
-            if (y1 == ys) wy += l1;
+            const float wy = bl_adjoint_weight(y0, y1, l1, ys);
             if (wy != 0.f) acc += wy * hbuf[fy * ws + x];
         }
         dx[(((size_t)b * Cm + c) * hs + ys) * ws + x] = acc;
@@ -142,17 +121,13 @@ __global__ __launch_bounds__(256) void bilinear_adjoint_gather_kernel(const floa
     for (int y = y_lo; y <= y_hi; ++y) {
         int y0, y1; float ly1;
         bl_tap(sy, hs, y, y0, y1, ly1);
-        float wy = 0.f;
-        if (y0 == ys) wy += 1.f - ly1;
-        if (y1 == ys) wy += ly1;
+        const float wy = bl_adjoint_weight(y0, y1, ly1, ys);
         if (wy == 0.f) continue;
         float racc = 0.f;
         for (int x = x_lo; x <= x_hi; ++x) {
             int x0, x1; float lx1;
             bl_tap(sx, ws, x, x0, x1, lx1);
-            float wx = 0.f;
-            if (x0 == xs) wx += 1.f - lx1;
-            if (x1 == xs) wx += lx1;
+            const float wx = bl_adjoint_weight(x0, x1, lx1, xs);
             if (wx != 0.f) {
                 float gv = g[(size_t)y * w0 + x];
                 if (MASKED) gv = a[(size_t)y * w0 + x] > 0.f ? gv : 0.f;

@@ -169,6 +169,22 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// Epilogue of a 256-thread block that reduces two values: the wave sums a and b of the four waves -> partial[2 * block] and
+// [2 * block + 1], added in the fixed order (0 + 1) + (2 + 3). red is the block's LDS scratch; every thread calls.
+template <class T>
+__device__ __forceinline__ void block_pair_to_partial(T a, T b, T (*red)[4], T* __restrict__ partial) {
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[2 * (size_t)blockIdx.x + 0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        partial[2 * (size_t)blockIdx.x + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    }
+}
 // inclusive prefix sum over the 64 lanes
 __device__ __forceinline__ int wave_incl_scan_i(int v, int lane) {
 #pragma unroll

@@ -1,41 +1,95 @@
 // Shared between upsample_ce.hip (weighted CE, mean over the sum of weights) and ohem.hip (CE over the mined pixels, mean over their
-// count): the cell decomposition of the bilinear(align_corners=True) upsampling -- see the head of upsample_ce.hip -- and the backward
-// kernel, which differs between the two only in the per-pixel coefficient (template flag OHEM). Internal linkage on purpose: each of
-// the two translation units instantiates its own kernels.
+// count): the cell softmax of the forward (one lane per label row and cell) and the backward kernel, which
+// differs between the two only in the per-pixel coefficient (template flag OHEM). Internal linkage on purpose: each of the two
+// translation units instantiates its own kernels.
 #pragma once
-#include "cseg_common.h"
+#include "cseg_taps.h"
 
 namespace {
 
 constexpr int BAND = 4;        // coarse rows per backward block
 constexpr int MAX_PX = 17;     // fine pixels per cell (upsampling factors up to 16x)
 
-struct CeDims {
-    int B, K, h, w, H, W;
-    float sy, sx;
+struct CeDims : UpDims {
     int ignore_label;
 };
 
-__host__ __device__ __forceinline__ int tap0(float s, int o) { return (int)(s * (float)o); }
+// one case per cell size the kernels are instantiated for (pick_px)
+#define CE_BY_PX(px, LAUNCH)           \
+    switch (px) {                      \
+        case 1: LAUNCH(1); break;      \
+        case 2: LAUNCH(2); break;      \
+        case 3: LAUNCH(3); break;      \
+        case 5: LAUNCH(5); break;      \
+        case 9: LAUNCH(9); break;      \
+        default: LAUNCH(17); break;    \
+    }
 
-__device__ __forceinline__ void tap(float s, int n_in, int o, int& i0, int& i1, float& l1) {
-    const float f = s * (float)o;
-    i0 = (int)f;
-    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    l1 = f - (float)i0;
-}
+// ---------------------------------------------------------------------------------------------------------
+// forward: the softmax statistics of one cell, global cell index g = (b * H + Y) * w + c
+// ---------------------------------------------------------------------------------------------------------
+// After softmax(), for the n label pixels at o0 .. o0 + n - 1: t = the label (-1: ignored or out of range, the latter counted in
+// status[1]), m + log(se) = the log-sum-exp, vt = the target logit, et = exp(vt - m) (WANT_ET only).
+template <int PX, bool WANT_ET>
+struct CeCell {
+    int n, t[PX];
+    size_t o0;
+    float m[PX], se[PX], vt[PX], et[WANT_ET ? PX : 1];
 
-// smallest o in [0, n_out] with tap0(s, o) >= c (n_out when there is none); tap0 is monotone in o
-__host__ __device__ __forceinline__ int first_with_tap(float s, int n_out, int c) {
-    if (c <= 0) return 0;
-    if (!(s > 0.f)) return n_out;
-    int o = (int)((float)c / s);
-    if (o > n_out) o = n_out;
-    if (o < 0) o = 0;
-    while (o > 0 && tap0(s, o - 1) >= c) --o;
-    while (o < n_out && tap0(s, o) < c) ++o;
-    return o;
-}
+    // false: the cell has no label pixel
+    __device__ __forceinline__ bool softmax(const float* __restrict__ seg, const int64_t* __restrict__ target, const CeDims& d, long g,
+                                            int32_t* __restrict__ status) {
+        const int c = (int)(g % d.w);
+        const long row = g / d.w;
+        const int Y = (int)(row % d.H), b = (int)(row / d.H);
+        const int Xs = first_with_tap(d.sx, d.W, c), Xe = first_with_tap(d.sx, d.W, c + 1);
+        n = min(Xe - Xs, PX);
+        if (n <= 0) return false;
+        int y0, y1;
+        float ly1;
+        bl_tap(d.sy, d.h, Y, y0, y1, ly1);
+        const float ly0 = 1.f - ly1;
+        const int c1 = c + (c < d.w - 1 ? 1 : 0);
+        float lx1[PX];
+        o0 = ((size_t)b * d.H + Y) * d.W + Xs;
+#pragma unroll
+        for (int p = 0; p < PX; ++p) {
+            lx1[p] = 0.f; m[p] = -INFINITY; se[p] = 0.f; vt[p] = 0.f; t[p] = -1;
+            if constexpr (WANT_ET) et[p] = 0.f;
+            if (p < n) {
+                lx1[p] = d.sx * (float)(Xs + p) - (float)c;
+                const int64_t t64 = target[o0 + p];
+                if (t64 != (int64_t)d.ignore_label) {
+                    if (t64 < 0 || t64 >= d.K) { if (status) atomicAdd(&status[1], 1); }
+                    else t[p] = (int)t64;
+                }
+            }
+        }
+        const float* s0 = seg + (((size_t)b * d.K) * d.h + y0) * d.w;
+        const float* s1 = seg + (((size_t)b * d.K) * d.h + y1) * d.w;
+        const size_t plane = (size_t)d.h * d.w;
+        for (int k = 0; k < d.K; ++k) {                       // pass 1: running max
+            const float r0 = ly0 * s0[k * plane + c] + ly1 * s1[k * plane + c];
+            const float r1 = ly0 * s0[k * plane + c1] + ly1 * s1[k * plane + c1];
+#pragma unroll
+            for (int p = 0; p < PX; ++p) m[p] = fmaxf(m[p], fmaf(lx1[p], r1 - r0, r0));
+        }
+        for (int k = 0; k < d.K; ++k) {                       // pass 2: sum of exponentials, target logit (and its exponential)
+            const float r0 = ly0 * s0[k * plane + c] + ly1 * s1[k * plane + c];
+            const float r1 = ly0 * s0[k * plane + c1] + ly1 * s1[k * plane + c1];
+#pragma unroll
+            for (int p = 0; p < PX; ++p) {
+                const float v = fmaf(lx1[p], r1 - r0, r0);
+                const float ev = __expf(v - m[p]);
+                se[p] += ev;
+                vt[p] = (k == t[p]) ? v : vt[p];
+                if constexpr (WANT_ET) et[p] = (k == t[p]) ? ev : et[p];
+            }
+        }
+        return true;
+    }
+    __device__ __forceinline__ float lse(int p) const { return m[p] + __logf(se[p]); }
+};
 
 // ---------------------------------------------------------------------------------------------------------
 // backward
@@ -92,7 +146,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ s
     for (int Y = Y_lo; Y < Y_hi; ++Y) {
         int y0, y1;
         float ly1;
-        tap(d.sy, d.h, Y, y0, y1, ly1);
+        bl_tap(d.sy, d.h, Y, y0, y1, ly1);
         const float ly0 = 1.f - ly1;
         while (y_cur < y0) {                 // the march is monotone: retire the finished coarse row
             flush_lo(y_cur);
@@ -177,12 +231,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ s
 }
 
 int make_dims(CeDims* d, int B, int K, int h, int w, int H, int W, int ignore_label) {
-    CSEG_REQUIRE(B > 0 && K > 0 && h > 0 && w > 0 && H > 0 && W > 0, "upsample_ce: empty shape");
-    CSEG_REQUIRE(H >= h && W >= w, "upsample_ce: only upsampling is supported (%dx%d -> %dx%d)", h, w, H, W);
-    d->B = B; d->K = K; d->h = h; d->w = w; d->H = H; d->W = W;
-    d->sy = ac_scale(h, H); d->sx = ac_scale(w, W);
     d->ignore_label = ignore_label;
-    return 1;
+    return up_dims("upsample_ce", d, B, K, h, w, H, W);
 }
 
 // largest number of fine pixels that share one left tap (host side, exact: same float arithmetic as the device)
@@ -240,14 +290,7 @@ int launch_ce_bwd(const char* what, const float* seg, const int64_t* target, con
         case 5: LAUNCH(P, 5); break;               \
         default: LAUNCH(P, 4); break;              \
     }
-    switch (px) {
-        case 1: BY_KG(1); break;
-        case 2: BY_KG(2); break;
-        case 3: BY_KG(3); break;
-        case 5: BY_KG(5); break;
-        case 9: BY_KG(9); break;
-        default: BY_KG(17); break;
-    }
+    CE_BY_PX(px, BY_KG);
 #undef BY_KG
 #undef LAUNCH
     CSEG_CHECK_LAUNCH("ce_bwd_kernel");

@@ -10,7 +10,7 @@
 // flat pixel index among equal e: the order of torch.sort(stable=True, descending=True). fg takes no part in the order.
 //
 // Launches (no block ever waits for another one: every cross-tile dependency is a launch boundary; no floating-point atomics):
-//   lov_errors_kernel   thread = one label pixel: interpolates the K logits (cseg_bilinear.h), softmax (max, then sum; logits in float64), keys of the
+//   lov_errors_kernel   thread = one label pixel: interpolates the K logits (taps: DESIGN.md section 26), softmax (max, then sum; logits in float64), keys of the
 //                       classes [k0, k0 + kn); optionally e / fg planes and the exact counts (integer atomics).
 //   lov_pack_kernel     e / fg planes (optionally gathered through a permutation) -> keys: the stage entry points of the tests.
 //   per radix pass (8 passes of 4 bits over bits 1..32):
@@ -24,9 +24,9 @@
 //                       the sign of d e / d p (-1 for fg, +1 otherwise, 0 where e == 0) to G_buf [K,P] f32 at the payload index.
 //   lov_finish_kernel   one block: loss_c, the number of present classes, the term.
 //   lov_pix_kernel      backward, thread = one label pixel: softmax statistics and D = sum_k p_k G_k
-//   lov_bwd_kernel      backward, thread = one coarse logit: gathers d z_c = p_c (G_c - D) over the label pixels whose bilinear taps
-//                       touch it (exact adjoint, as rmi_bwd_kernel), times d_loss / n_present.
-#include "cseg_bilinear.h"
+//   lov_bwd_kernel      backward, thread = one coarse logit: the gather adjoint (bl_gather_adjoint) of
+//                       d z_c = p_c (G_c - D), times d_loss / n_present.
+#include "cseg_taps.h"
 
 namespace {
 
@@ -41,9 +41,8 @@ constexpr unsigned LV_VOID = LV_ONE + 1u;           // sort field of an invalid 
 
 __device__ __forceinline__ int lv_idx(int i) { return i + (i >> 4); }
 
-struct LvDims {
-    int B, K, h, w, H, W, P;
-    float sy, sx;
+struct LvDims : UpDims {
+    int P;
 };
 
 __device__ __forceinline__ unsigned lv_pack(float e, unsigned fg) {
@@ -62,7 +61,7 @@ struct LvTap {
     float ly1, lx1;
 };
 
-// One interpolated logit in float64 from the fp32 taps and the fp32 weights of cseg_bilinear.h (torch's own index arithmetic, so the
+// One interpolated logit in float64 from the fp32 taps and the fp32 weights of cseg_taps.h (torch's own index arithmetic, so the
 // weights are torch's): the rounding of an fp32 interpolation is one ulp of the logit, which at |x| ~ 100 is 1e-5 of a probability --
 // more than the reference's own fp32 deviation on some inputs. Only differences and explicit fma: nothing is left for the compiler to
 // contract one way in one inlined copy and another way in the next (the passes below rely on equal inputs giving equal values).
@@ -96,12 +95,6 @@ __device__ __forceinline__ void lv_pixel(const LvDims& d, int i, int& b, LvTap& 
     b = r / d.H;
     bl_tap(d.sy, d.h, Y, t.y0, t.y1, t.ly1);
     bl_tap(d.sx, d.w, X, t.x0, t.x1, t.lx1);
-}
-
-__device__ __forceinline__ double lv_wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 __global__ __launch_bounds__(256) void lov_zero_kernel(int* __restrict__ p, int n) {
@@ -357,7 +350,7 @@ __global__ __launch_bounds__(LV_THREADS) void lov_apply_kernel(const unsigned* _
             if ((unsigned)px < (unsigned)P) gbuf[row + px] = e > 0.f ? (float)(fg ? -g : g) : 0.f;
         }
     }
-    acc = lv_wave_sum_d(acc);
+    acc = wave_sum_d(acc);
     if (lane == 0) s_red[wave] = acc;
     __syncthreads();
     if (tid == 0) partial[(size_t)c * T + tile] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
@@ -428,45 +421,26 @@ __global__ __launch_bounds__(256) void lov_bwd_kernel(const float* __restrict__ 
     if (cell >= d.h * d.w) return;
     const int ys = cell / d.w, xs = cell - ys * d.w;
     const float scale = outd[1] > 0.0 ? (float)((double)d_loss[0] / outd[1]) : 0.f;
-    int y_lo, y_hi, x_lo, x_hi;
-    bl_fine_range(d.sy, d.H, ys, ys, y_lo, y_hi);
-    bl_fine_range(d.sx, d.W, xs, xs, x_lo, x_hi);
     const float* plane = seg + ((size_t)b * d.K + k) * d.h * d.w;
     const float* grow = gbuf + (size_t)k * d.P;
-    float acc = 0.f;
-    for (int Y = y_lo; Y <= y_hi; ++Y) {
-        LvTap t;
-        bl_tap(d.sy, d.h, Y, t.y0, t.y1, t.ly1);
-        float wy = 0.f;
-        if (t.y0 == ys) wy += 1.f - t.ly1;
-        if (t.y1 == ys) wy += t.ly1;
-        if (wy == 0.f) continue;
-        float racc = 0.f;
-        for (int X = x_lo; X <= x_hi; ++X) {
-            bl_tap(d.sx, d.w, X, t.x0, t.x1, t.lx1);
-            float wx = 0.f;
-            if (t.x0 == xs) wx += 1.f - t.lx1;
-            if (t.x1 == xs) wx += t.lx1;
-            if (wx == 0.f) continue;
-            const size_t i = ((size_t)b * d.H + Y) * d.W + X;
-            const float s = stats[(size_t)d.P + i];
-            if (!(s > 0.f)) continue;                              // invalid pixel
-            const float p = fminf(lv_exp(lv_logit(plane, d.w, t), stats[i]) / s, 1.f);
-            racc += wx * (p * (grow[i] - stats[2 * (size_t)d.P + i]));
-        }
-        acc += wy * racc;
-    }
+    const float acc = bl_gather_adjoint(d.sy, d.sx, d.h, d.w, d.H, d.W, ys, xs,
+                                        [&](int Y, int X, int y0, int y1, float ly1, int x0, int x1, float lx1, float& v) {
+        const size_t i = ((size_t)b * d.H + Y) * d.W + X;
+        const float s = stats[(size_t)d.P + i];
+        if (!(s > 0.f)) return false;                              // invalid pixel
+        const float p = fminf(lv_exp(lv_logit(plane, d.w, LvTap{y0, y1, x0, x1, ly1, lx1}), stats[i]) / s, 1.f);
+        v = p * (grow[i] - stats[2 * (size_t)d.P + i]);
+        return true;
+    });
     d_seg[(((size_t)b * d.K + k) * d.h + ys) * d.w + xs] = acc * scale;
 }
 
 int lov_dims(LvDims* d, int B, int K, int h, int w, int H, int W) {
-    CSEG_REQUIRE(B > 0 && K > 0 && h > 0 && w > 0 && H > 0 && W > 0, "lovasz: empty shape");
+    if (!up_dims("lovasz", d, B, K, h, w, H, W)) return 0;
     CSEG_REQUIRE(K <= 256, "lovasz: %d classes (at most 256 are implemented)", K);
-    CSEG_REQUIRE(H >= h && W >= w, "lovasz: only upsampling is supported (%dx%d -> %dx%d)", h, w, H, W);
     CSEG_REQUIRE((long)B * H * W < 2147483648L, "lovasz: %ld label pixels (P = B * H * W must be below 2^31)", (long)B * H * W);
     CSEG_REQUIRE((long)B * K * h * w < 2147483647L, "lovasz: tensor too large");
-    d->B = B; d->K = K; d->h = h; d->w = w; d->H = H; d->W = W; d->P = B * H * W;
-    d->sy = ac_scale(h, H); d->sx = ac_scale(w, W);
+    d->P = B * H * W;
     return 1;
 }
 

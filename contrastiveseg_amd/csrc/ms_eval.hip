@@ -8,7 +8,7 @@
 //
 // ms_fuse_kernel   one thread per output pixel. The taps of every term (row offsets, columns, blend factors; for the flipped map
 //                  the taps of the MIRRORED output column W-1-x, which is what flipping the upsampled map means) are computed once
-//                  with the package's fp32 index arithmetic (ac_scale, bl_tap) and stay in registers: the term loop is unrolled
+//                  with the package's fp32 index arithmetic (bl_tap) and stay in registers: the term loop is unrolled
 //                  to the template's NT. Classes run in the outer loop, terms inside, in the reference's association order
 //                      v = 0;  v = v + w_i * (U(a_i)[y,x] + U(b_i)[y,W-1-x])
 //                  with a running (best, index) pair: no per-thread array over K. Strict '>' keeps the first index among equal
@@ -18,7 +18,7 @@
 // confusion_*      integer counts, exact. K <= 128: per-block histogram of K*K 32-bit bins in LDS, non-zero bins flushed with one
 //                  64-bit global atomic per bin and block. Above: lanes that hold runs of equal (gt, pred) pairs -- neighbouring
 //                  pixels mostly do -- are merged with a segmented scan over the wave, one global atomic per run.
-#include "cseg_bilinear.h"
+#include "cseg_taps.h"
 
 namespace {
 

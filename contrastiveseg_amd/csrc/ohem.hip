@@ -10,7 +10,7 @@
 // 12 (of which [0, 1] uses the values 0 .. 0x3F8) / 10 / 10 bits, 1024 bins each.
 // Launches (no block waits for another one; integer atomics only, so every count is exact and nothing depends on arrival order):
 //   ohem_zero_kernel    the three histograms and the state words <- 0 (a kernel, not hipMemsetAsync: DESIGN.md section 20.6)
-//   ohem_prob_kernel    the forward of ce_fwd_kernel (one lane per label row and cell) -> p, nll = lse - v_t, lse per label pixel (p = 2 at
+//   ohem_prob_kernel    the cell softmax of ce_fwd_kernel (CeCell) -> p, nll = lse - v_t, lse per label pixel (p = 2 at
 //                       invalid pixels), the level-0 histogram (block-private LDS bins, one lane merges the equal bins of its cell before
 //                       the LDS atomic, non-empty bins flushed with global atomics) and #{p < thresh}
 //   ohem_pick_kernel    one block, one thread per bin: prefix sum of a level's histogram -> the bin that holds rank k and the rank inside
@@ -67,82 +67,35 @@ __global__ __launch_bounds__(256) void ohem_prob_kernel(const float* __restrict_
     for (int i = threadIdx.x; i < OH_BINS; i += 256) s_hist[i] = 0;
     __syncthreads();
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
-    const long n_cells = (long)d.B * d.H * d.w;
     int below = 0;
-    if (g < n_cells) {
-        const int c = (int)(g % d.w);
-        const long row = g / d.w;
-        const int Y = (int)(row % d.H), b = (int)(row / d.H);
-        const int Xs = first_with_tap(d.sx, d.W, c), Xe = first_with_tap(d.sx, d.W, c + 1);
-        const int n = min(Xe - Xs, PX);
-        if (n > 0) {
-            int y0, y1;
-            float ly1;
-            tap(d.sy, d.h, Y, y0, y1, ly1);
-            const float ly0 = 1.f - ly1;
-            const int c1 = c + (c < d.w - 1 ? 1 : 0);
-            float lx1[PX], m[PX], se[PX], vt[PX], et[PX];
-            int t[PX];
-            const size_t o0 = ((size_t)b * d.H + Y) * d.W + Xs;
+    CeCell<PX, true> cell;
+    if (g < (long)d.B * d.H * d.w && cell.softmax(seg, target, d, g, status)) {
+        const size_t o0 = cell.o0;
+        int cur = -1, cnt = 0;                                    // run of equal bins inside the cell: one LDS atomic per run
 #pragma unroll
-            for (int p = 0; p < PX; ++p) {
-                lx1[p] = 0.f; m[p] = -INFINITY; se[p] = 0.f; vt[p] = 0.f; et[p] = 0.f; t[p] = -1;
-                if (p < n) {
-                    lx1[p] = d.sx * (float)(Xs + p) - (float)c;
-                    const int64_t t64 = target[o0 + p];
-                    if (t64 != (int64_t)d.ignore_label) {
-                        if (t64 < 0 || t64 >= d.K) { if (status) atomicAdd(&status[1], 1); }
-                        else t[p] = (int)t64;
+        for (int p = 0; p < PX; ++p) {
+            if (p < cell.n) {
+                const float lse = cell.lse(p);
+                float pv = OH_SENTINEL, nl = 0.f;
+                if (cell.t[p] >= 0) {
+                    pv = cell.et[p] / cell.se[p];                 // et is one of the non-negative terms of se: 0 <= p <= 1
+                    nl = lse - cell.vt[p];                        // not -log p: stays finite where p underflows to 0
+                }
+                p_out[o0 + p] = pv;
+                nll_out[o0 + p] = nl;
+                if (lse_out) lse_out[o0 + p] = lse;
+                if (pv <= 1.0f) {
+                    below += pv < thresh ? 1 : 0;
+                    const int bin = oh_bin0(pv);
+                    if (bin != cur) {
+                        if (cnt) atomicAdd(&s_hist[cur], cnt);
+                        cur = bin; cnt = 0;
                     }
+                    ++cnt;
                 }
             }
-            const float* s0 = seg + (((size_t)b * d.K) * d.h + y0) * d.w;
-            const float* s1 = seg + (((size_t)b * d.K) * d.h + y1) * d.w;
-            const size_t plane = (size_t)d.h * d.w;
-            for (int k = 0; k < d.K; ++k) {                       // pass 1: running max
-                const float r0 = ly0 * s0[k * plane + c] + ly1 * s1[k * plane + c];
-                const float r1 = ly0 * s0[k * plane + c1] + ly1 * s1[k * plane + c1];
-#pragma unroll
-                for (int p = 0; p < PX; ++p) m[p] = fmaxf(m[p], fmaf(lx1[p], r1 - r0, r0));
-            }
-            for (int k = 0; k < d.K; ++k) {                       // pass 2: sum of exponentials, target logit and its exponential
-                const float r0 = ly0 * s0[k * plane + c] + ly1 * s1[k * plane + c];
-                const float r1 = ly0 * s0[k * plane + c1] + ly1 * s1[k * plane + c1];
-#pragma unroll
-                for (int p = 0; p < PX; ++p) {
-                    const float v = fmaf(lx1[p], r1 - r0, r0);
-                    const float ev = __expf(v - m[p]);
-                    se[p] += ev;
-                    vt[p] = (k == t[p]) ? v : vt[p];
-                    et[p] = (k == t[p]) ? ev : et[p];
-                }
-            }
-            int cur = -1, cnt = 0;                                // run of equal bins inside the cell: one LDS atomic per run
-#pragma unroll
-            for (int p = 0; p < PX; ++p) {
-                if (p < n) {
-                    const float lse = m[p] + __logf(se[p]);
-                    float pv = OH_SENTINEL, nl = 0.f;
-                    if (t[p] >= 0) {
-                        pv = et[p] / se[p];                       // et is one of the non-negative terms of se: 0 <= p <= 1
-                        nl = lse - vt[p];                         // not -log p: stays finite where p underflows to 0
-                    }
-                    p_out[o0 + p] = pv;
-                    nll_out[o0 + p] = nl;
-                    if (lse_out) lse_out[o0 + p] = lse;
-                    if (pv <= 1.0f) {
-                        below += pv < thresh ? 1 : 0;
-                        const int bin = oh_bin0(pv);
-                        if (bin != cur) {
-                            if (cnt) atomicAdd(&s_hist[cur], cnt);
-                            cur = bin; cnt = 0;
-                        }
-                        ++cnt;
-                    }
-                }
-            }
-            if (cnt) atomicAdd(&s_hist[cur], cnt);
         }
+        if (cnt) atomicAdd(&s_hist[cur], cnt);
     }
     oh_flush(s_hist, s_red, below, true, sel, sel + OH_STATE);
 }
@@ -304,14 +257,7 @@ extern "C" int cseg_ohem_prob(const float* seg, const int64_t* target, int ignor
     const long n_cells = (long)B * H * w;
     const int n_blocks = (int)((n_cells + 255) / 256);
 #define LAUNCH(P) hipLaunchKernelGGL(ohem_prob_kernel<P>, dim3(n_blocks), dim3(256), 0, stream, seg, target, d, thresh, p, nll, lse, sel, status)
-    switch (px) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        case 5: LAUNCH(5); break;
-        case 9: LAUNCH(9); break;
-        default: LAUNCH(17); break;
-    }
+    CE_BY_PX(px, LAUNCH);
 #undef LAUNCH
     CSEG_CHECK_LAUNCH("ohem_prob_kernel");
     return 1;

@@ -5,7 +5,7 @@
 //
 // Launches (all deterministic: fixed-order block partials, no floating-point atomics):
 //   rmi_pool_kernel    thread = one pooled cell of one (image, class): the 3 x 3 window's nine label pixels are interpolated from the
-//                      coarse logits with the package's fp32 index arithmetic (cseg_bilinear.h), each contributes its BCE term, the
+//                      coarse logits with the package's fp32 index arithmetic, each contributes its BCE term, the
 //                      window maximum of sigmoid * valid + 1e-6 goes to p_pool (f32), the winning slot to route (u8), "some pixel of
 //                      the window carries this class" to l_pool (u8). Padding never wins; the first slot in row-major order wins
 //                      among equal maxima (F.max_pool2d).
@@ -17,9 +17,9 @@
 //                      d rmi / d Clp (derivation in DESIGN.md; the + 1e-8 inside the log is kept by differentiating the factor).
 //   rmi_finish_kernel  one block: BCE sum, V, sum of rmi in fixed order -> the loss.
 //   rmi_gpool_kernel   thread = one pooled cell: the 9 x 9 stencil that carries the matrix gradients back to p_pool.
-//   rmi_bwd_kernel     thread = one coarse logit: walks the label pixels whose bilinear taps touch it (exact adjoint, gather form),
-//                      per pixel the BCE gradient plus, for the routed pixel of its window, g_pool * sigmoid'.
-#include "cseg_bilinear.h"
+//   rmi_bwd_kernel     thread = one coarse logit: the gather adjoint (its own copy of the loop nest) of, per label
+//                      pixel, the BCE gradient plus, for the routed pixel of its window, g_pool * sigmoid'.
+#include "cseg_taps.h"
 
 namespace {
 
@@ -44,12 +44,6 @@ __device__ __forceinline__ float rmi_logit(const float* __restrict__ plane, int 
 }
 
 __device__ __forceinline__ float rmi_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // pool forward
@@ -110,14 +104,7 @@ __global__ __launch_bounds__(256) void rmi_pool_kernel(const float* __restrict__
         route[g] = (uint8_t)slot;
         l_pool[g] = (uint8_t)lab;
     }
-    bce = wave_sum_d(bce);
-    nvalid = wave_sum_d(nvalid);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = bce; red[1][threadIdx.x >> 6] = nvalid; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * (size_t)blockIdx.x + 0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        partial[2 * (size_t)blockIdx.x + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    }
+    block_pair_to_partial(wave_sum_d(bce), wave_sum_d(nvalid), red, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -419,9 +406,7 @@ __global__ __launch_bounds__(256) void rmi_bwd_kernel(const float* __restrict__ 
         int y0, y1;
         float ly1;
         bl_tap(d.sy, d.h, Y, y0, y1, ly1);
-        float wy = 0.f;
-        if (y0 == ys) wy += 1.f - ly1;
-        if (y1 == ys) wy += ly1;
+        const float wy = bl_adjoint_weight(y0, y1, ly1, ys);
         if (wy == 0.f) continue;
         const int py = (Y + 1) / 3, sy3 = (Y + 1) - 3 * py;
         float racc = 0.f;
@@ -429,9 +414,7 @@ __global__ __launch_bounds__(256) void rmi_bwd_kernel(const float* __restrict__ 
             int x0, x1;
             float lx1;
             bl_tap(d.sx, d.w, X, x0, x1, lx1);
-            float wx = 0.f;
-            if (x0 == xs) wx += 1.f - lx1;
-            if (x1 == xs) wx += lx1;
+            const float wx = bl_adjoint_weight(x0, x1, lx1, xs);
             if (wx == 0.f) continue;
             const int64_t t64 = tplane[(size_t)Y * d.W + X];
             if (t64 < 0 || t64 >= d.K) continue;                  // invalid pixels: p is the constant 1e-6, no BCE term
@@ -449,14 +432,12 @@ __global__ __launch_bounds__(256) void rmi_bwd_kernel(const float* __restrict__ 
 }
 
 int rmi_dims(RmiDims* d, int B, int K, int h, int w, int H, int W) {
-    CSEG_REQUIRE(B > 0 && K > 0 && h > 0 && w > 0 && H > 0 && W > 0, "rmi: empty shape");
-    CSEG_REQUIRE(H >= h && W >= w, "rmi: only upsampling is supported (%dx%d -> %dx%d)", h, w, H, W);
-    d->B = B; d->K = K; d->h = h; d->w = w; d->H = H; d->W = W;
-    d->hp = (H - 1) / 3 + 1; d->wp = (W - 1) / 3 + 1;
+    UpDims u;
+    if (!up_dims("rmi", &u, B, K, h, w, H, W)) return 0;
+    *d = RmiDims{B, K, h, w, H, W, (H - 1) / 3 + 1, (W - 1) / 3 + 1, u.sy, u.sx};
     CSEG_REQUIRE(d->hp >= 3 && d->wp >= 3, "rmi: the pooled map is %d x %d (labels %d x %d); the 3 x 3 neighbourhood needs at least "
                  "3 x 3 (the reference yields NaN there)", d->hp, d->wp, H, W);
     CSEG_REQUIRE((long)B * K * d->hp * d->wp < 2147483647L && (long)B * K * h * w < 2147483647L, "rmi: tensor too large");
-    d->sy = ac_scale(h, H); d->sx = ac_scale(w, W);
     return 1;
 }
 

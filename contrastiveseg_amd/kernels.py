@@ -11,7 +11,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _hip
 
-I32, I16, I64, F32 = torch.int32, torch.int16, torch.int64, torch.float32
+I32, I16, I64, F32, F64, U8 = torch.int32, torch.int16, torch.int64, torch.float32, torch.float64, torch.uint8
 
 
 def _p(t, dtype, what):
@@ -20,6 +20,10 @@ def _p(t, dtype, what):
 
 def _null():
     return ctypes.c_void_p(None)
+
+
+def _opt(t, dtype, what):
+    return _p(t, dtype, what) if t is not None else _null()
 
 
 def _on_device(t):
@@ -678,6 +682,29 @@ def fan_out(x, n):
 
 
 # ----------------------------------------------------------------------------------------------------------
+# segmentation terms on the bilinear(align_corners=True) upsampling of coarse logits, which is never built
+# ----------------------------------------------------------------------------------------------------------
+def _seg_term_shapes(what, seg, target, max_classes=None):
+    """seg [B,K,h,w] / target [B,H,W] -> B, K, h, w, H, W, P = B * H * W, with the refusals the terms share (before any device check)."""
+    if seg.dim() != 4 or target.dim() != 3 or target.shape[0] != seg.shape[0]:
+        raise RuntimeError("%s: seg %s / target %s, expected [B,K,h,w] / [B,H,W]" % (what, tuple(seg.shape), tuple(target.shape)))
+    B, K, h, w = seg.shape
+    _, H, W = target.shape
+    if B * H * W >= 2 ** 31:
+        raise RuntimeError("%s: %d label pixels (P = B * H * W must be below 2^31)" % (what, B * H * W))
+    if max_classes is not None and K > max_classes:
+        raise RuntimeError("%s: %d classes (at most %d are implemented)" % (what, K, max_classes))
+    if H < h or W < w:
+        raise RuntimeError("%s: only upsampling is supported (%dx%d -> %dx%d)" % (what, h, w, H, W))
+    return B, K, h, w, H, W, B * H * W
+
+
+def _d_loss(g):
+    """The incoming gradient of a scalar term as the f32 [1] buffer the backward entry points read."""
+    return g.reshape(1).to(F32).contiguous()
+
+
+# ----------------------------------------------------------------------------------------------------------
 # segmentation term: upsample + weighted CE
 # ----------------------------------------------------------------------------------------------------------
 class UpsampleCE(Function):
@@ -696,10 +723,9 @@ class UpsampleCE(Function):
         out = torch.empty(2, dtype=F32, device=dev)
         if status is None:
             status = torch.zeros(4, dtype=I32, device=dev)
-        wp = _p(weight, F32, "ce_weight") if weight is not None else _null()
         lse = torch.empty(B, H, W, dtype=F32, device=dev)      # per-label-pixel log-sum-exp, reused by the backward
-        _hip.call("cseg_upsample_ce_fwd", _p(seg, F32, "seg"), _p(target, I64, "target"), wp, int(ignore_index), B, K,
-                  h, w, H, W, _p(partial, F32, "partial"), _p(out, F32, "out"), _p(status, I32, "status"),
+        _hip.call("cseg_upsample_ce_fwd", _p(seg, F32, "seg"), _p(target, I64, "target"), _opt(weight, F32, "ce_weight"), int(ignore_index),
+                  B, K, h, w, H, W, _p(partial, F32, "partial"), _p(out, F32, "out"), _p(status, I32, "status"),
                   _p(lse, F32, "lse"), _hip.stream_ptr())
         ctx.save_for_backward(seg, target, out, lse)
         ctx.weight = weight
@@ -712,11 +738,10 @@ class UpsampleCE(Function):
         B, K, h, w = seg.shape
         _, H, W = target.shape
         d_seg = torch.empty_like(seg)
-        g = g.reshape(1).to(F32).contiguous()
-        wp = _p(ctx.weight, F32, "ce_weight") if ctx.weight is not None else _null()
-        _hip.call("cseg_upsample_ce_bwd", _p(seg, F32, "seg"), _p(target, I64, "target"), wp, ctx.ignore_index, B, K,
-                  h, w, H, W, _p(out, F32, "out"), _p(g, F32, "d_loss"), _p(lse, F32, "lse"), _p(d_seg, F32, "d_seg"),
-              _hip.stream_ptr())
+        g = _d_loss(g)
+        _hip.call("cseg_upsample_ce_bwd", _p(seg, F32, "seg"), _p(target, I64, "target"), _opt(ctx.weight, F32, "ce_weight"),
+                  ctx.ignore_index, B, K, h, w, H, W, _p(out, F32, "out"), _p(g, F32, "d_loss"), _p(lse, F32, "lse"),
+                  _p(d_seg, F32, "d_seg"), _hip.stream_ptr())
         return d_seg, None, None, None, None
 
 
@@ -730,10 +755,6 @@ def upsample_ce(seg, target, weight=None, ignore_index=-1, status=None):
 # ----------------------------------------------------------------------------------------------------------
 # segmentation term: upsample + region mutual information (csrc/rmi.hip)
 # ----------------------------------------------------------------------------------------------------------
-U8 = torch.uint8
-F64 = torch.float64
-
-
 def rmi_pooled_size(H, W):
     """F.max_pool2d(kernel 3, stride 3, padding 1) of an H x W map."""
     return (int(H) - 1) // 3 + 1, (int(W) - 1) // 3 + 1
@@ -744,11 +765,8 @@ def rmi_pool(seg, target, radius=3, pool_way=0, pool_size=3, pool_stride=3):
     """seg [B,K,h,w] f32 (coarse logits), target [B,H,W] i64 -> p_pool f32, route u8, l_pool u8 (each [B,K,hp,wp]) and the
     per-block partials f64 [nb, 2] of (BCE sum, valid pixels): the pooled maps of lib/loss/rmi_loss.py:315-340 applied to the
     bilinear(align_corners=True) upsampling of seg, which is never built."""
-    if seg.dim() != 4 or target.dim() != 3 or target.shape[0] != seg.shape[0]:
-        raise RuntimeError("rmi_pool: seg %s / target %s, expected [B,K,h,w] / [B,H,W]" % (tuple(seg.shape), tuple(target.shape)))
+    B, K, h, w, H, W, _ = _seg_term_shapes("rmi_pool", seg, target)
     seg, target = seg.contiguous(), target.contiguous()
-    B, K, h, w = seg.shape
-    _, H, W = target.shape
     hp, wp = rmi_pooled_size(H, W)
     dev = seg.device
     nb = max(_hip.lib().cseg_rmi_pool_blocks(B, K, H, W), 1)
@@ -821,7 +839,7 @@ class UpsampleRMI(Function):
         _, H, W = target.shape
         d_seg = torch.empty_like(seg)
         g_pool = torch.empty_like(p_pool)
-        g = g.reshape(1).to(F32).contiguous()
+        g = _d_loss(g)
         lam, lambda_way, loss_weight = ctx.coef
         _hip.call("cseg_rmi_bwd", _p(seg, F32, "seg"), _p(target, I64, "target"), _pf(p_pool), _pf(route), _pf(l_pool), _pf(means),
                   _pf(grads), _pf(outd), _p(g, F32, "d_loss"), B, K, h, w, H, W, lam, lambda_way, loss_weight, _pf(g_pool), _pf(d_seg),
@@ -832,8 +850,7 @@ class UpsampleRMI(Function):
 def rmi_loss(seg, target, lam=0.5, lambda_way=1, loss_weight=1.0, want_terms=False):
     """The RMI segmentation term on coarse (or label-resolution) logits. With want_terms also the f64 [4] device tensor
     {loss, bce, rmi_loss, V}. Works under torch.no_grad() (the validation pass calls the criterion that way)."""
-    if seg.dim() != 4 or target.dim() != 3 or target.shape[0] != seg.shape[0]:
-        raise RuntimeError("rmi_loss: seg %s / target %s, expected [B,K,h,w] / [B,H,W]" % (tuple(seg.shape), tuple(target.shape)))
+    _seg_term_shapes("rmi_loss", seg, target)
     loss, outd = UpsampleRMI.apply(seg, target, lam, lambda_way, loss_weight)
     return (loss, outd) if want_terms else loss
 
@@ -845,20 +862,6 @@ def rmi_loss(seg, target, lam=0.5, lambda_way=1, loss_weight=1.0, want_terms=Fal
 # (DESIGN.md section 21). The result does not depend on it.
 LOVASZ_CLASS_CHUNK = 4
 LOVASZ_MAX_CLASSES = 256
-
-
-def _lovasz_shapes(what, seg, target):
-    if seg.dim() != 4 or target.dim() != 3 or target.shape[0] != seg.shape[0]:
-        raise RuntimeError("%s: seg %s / target %s, expected [B,K,h,w] / [B,H,W]" % (what, tuple(seg.shape), tuple(target.shape)))
-    B, K, h, w = seg.shape
-    _, H, W = target.shape
-    if B * H * W >= 2 ** 31:
-        raise RuntimeError("%s: %d label pixels (P = B * H * W must be below 2^31)" % (what, B * H * W))
-    if K > LOVASZ_MAX_CLASSES:
-        raise RuntimeError("%s: %d classes (at most %d are implemented)" % (what, K, LOVASZ_MAX_CLASSES))
-    if H < h or W < w:
-        raise RuntimeError("%s: only upsampling is supported (%dx%d -> %dx%d)" % (what, h, w, H, W))
-    return B, K, h, w, H, W, B * H * W
 
 
 def _lovasz_planes(what, P_shape, **planes):
@@ -876,14 +879,14 @@ def lovasz_errors(seg, target, ignore_index=-1, status=None):
     """seg [B,K,h,w] f32 (coarse logits), target [B,H,W] i64 -> e f32 [K,P] = |fg - softmax(bilinear(seg))| per class at the P = B H W
     label pixels (-1 at pixels whose label is not in [0, K)), fg u8 [K,P], counts i32 [K+2]: fg pixels per class, valid pixels, labels
     that are neither `ignore_index` nor a class id (also added to status[1] when `status` i32 [4] is given)."""
-    B, K, h, w, H, W, P = _lovasz_shapes("lovasz_errors", seg, target)
+    B, K, h, w, H, W, P = _seg_term_shapes("lovasz_errors", seg, target, LOVASZ_MAX_CLASSES)
     seg, target = seg.contiguous(), target.contiguous()
     dev = seg.device
     e = torch.empty(K, P, dtype=F32, device=dev)
     fg = torch.empty(K, P, dtype=U8, device=dev)
     counts = torch.empty(K + 2, dtype=I32, device=dev)
     _hip.call("cseg_lovasz_errors", _p(seg, F32, "seg"), _p(target, I64, "target"), int(ignore_index), B, K, h, w, H, W, 0, K, _null(),
-              _pf(e), _pf(fg), _pf(counts), _p(status, I32, "status") if status is not None else _null(), _hip.stream_ptr())
+              _pf(e), _pf(fg), _pf(counts), _opt(status, I32, "status"), _hip.stream_ptr())
     return e, fg, counts
 
 
@@ -939,10 +942,10 @@ class UpsampleLovasz(Function):
 
     @staticmethod
     def forward(ctx, seg, target, ignore_index, status, want_grad):
-        B, K, h, w, H, W, P = _lovasz_shapes("lovasz_softmax", seg, target)
+        B, K, h, w, H, W, P = _seg_term_shapes("lovasz_softmax", seg, target, LOVASZ_MAX_CLASSES)
         seg, target = seg.contiguous(), target.contiguous()
         sp, tp = _p(seg, F32, "seg"), _p(target, I64, "target")
-        stp = _p(status, I32, "status") if status is not None else _null()
+        stp = _opt(status, I32, "status")
         dev = seg.device
         T = _hip.lib().cseg_lovasz_tiles(P)
         chunk = max(1, min(int(LOVASZ_CLASS_CHUNK), K))
@@ -976,7 +979,7 @@ class UpsampleLovasz(Function):
         _, H, W = target.shape
         d_seg = torch.empty_like(seg)
         stats = torch.empty(3, B * H * W, dtype=F32, device=seg.device)
-        g = g.reshape(1).to(F32).contiguous()
+        g = _d_loss(g)
         _hip.call("cseg_lovasz_bwd", _p(seg, F32, "seg"), _p(target, I64, "target"), _pf(gbuf), _pf(outd), _p(g, F32, "d_loss"), B, K, h, w,
                   H, W, _pf(stats), _pf(d_seg), _hip.stream_ptr())
         return d_seg, None, None, None, None
@@ -999,32 +1002,19 @@ OHEM_SENTINEL = 2.0      # p at a pixel whose label is not in [0, K): above ever
 _OHEM_STATE = 3 * 1024   # sel = three histograms of 1024 bins, then the state words {#{p < thresh}, n, k, prefix, rank, done, kth, thr}
 
 
-def _ohem_shapes(what, seg, target):
-    if seg.dim() != 4 or target.dim() != 3 or target.shape[0] != seg.shape[0]:
-        raise RuntimeError("%s: seg %s / target %s, expected [B,K,h,w] / [B,H,W]" % (what, tuple(seg.shape), tuple(target.shape)))
-    B, K, h, w = seg.shape
-    _, H, W = target.shape
-    if B * H * W >= 2 ** 31:
-        raise RuntimeError("%s: %d label pixels (P = B * H * W must be below 2^31)" % (what, B * H * W))
-    if H < h or W < w:
-        raise RuntimeError("%s: only upsampling is supported (%dx%d -> %dx%d)" % (what, h, w, H, W))
-    return B, K, h, w, H, W, B * H * W
-
-
 def _ohem_sel(dev):
     return torch.empty(_hip.lib().cseg_ohem_sel_ints(), dtype=I32, device=dev)
 
 
 def _ohem_prob(seg, target, ignore_index, thresh, status, want_lse):
-    B, K, h, w, H, W, P = _ohem_shapes("ohem_prob", seg, target)
+    B, K, h, w, H, W, P = _seg_term_shapes("ohem_prob", seg, target)
     seg, target = seg.contiguous(), target.contiguous()
     dev = seg.device
     p, nll = torch.empty(B, H, W, dtype=F32, device=dev), torch.empty(B, H, W, dtype=F32, device=dev)
     lse = torch.empty(B, H, W, dtype=F32, device=dev) if want_lse else None
     sel = _ohem_sel(dev)
     _hip.call("cseg_ohem_prob", _p(seg, F32, "seg"), _p(target, I64, "target"), int(ignore_index), B, K, h, w, H, W, float(thresh), _pf(p),
-              _pf(nll), _pf(lse) if lse is not None else _null(), _pf(sel), _p(status, I32, "status") if status is not None else _null(),
-              _hip.stream_ptr())
+              _pf(nll), _pf(lse) if lse is not None else _null(), _pf(sel), _opt(status, I32, "status"), _hip.stream_ptr())
     return p, nll, lse, sel
 
 
@@ -1061,8 +1051,8 @@ def _ohem_reduce(p, nll, target, weight, K, sel):
     pcount = torch.empty(nb, dtype=I32, device=dev)
     out = torch.empty(4, dtype=F32, device=dev)
     outi = torch.empty(4, dtype=I32, device=dev)
-    _hip.call("cseg_ohem_reduce", _pf(p), _pf(nll), _p(target, I64, "target"), _p(weight, F32, "ce_weight") if weight is not None else _null(),
-              int(K), P, _pf(sel), _pf(partial), _pf(pcount), _pf(out), _pf(outi), _hip.stream_ptr())
+    _hip.call("cseg_ohem_reduce", _pf(p), _pf(nll), _p(target, I64, "target"), _opt(weight, F32, "ce_weight"), int(K), P,
+              _pf(sel), _pf(partial), _pf(pcount), _pf(out), _pf(outi), _hip.stream_ptr())
     return out, outi
 
 
@@ -1085,7 +1075,7 @@ class OhemCE(Function):
 
     @staticmethod
     def forward(ctx, seg, target, weight, ignore_index, thresh, min_kept, status, want_grad):
-        B, K, h, w, H, W, P = _ohem_shapes("ohem_ce", seg, target)
+        B, K, h, w, H, W, P = _seg_term_shapes("ohem_ce", seg, target)
         seg, target = seg.contiguous(), target.contiguous()
         p, nll, lse, sel = _ohem_prob(seg, target, ignore_index, thresh, status, want_grad)
         _hip.call("cseg_ohem_select", _pf(p), P, float(thresh), int(min_kept), 1, 1, _pf(sel), _hip.stream_ptr())
@@ -1104,10 +1094,9 @@ class OhemCE(Function):
         B, K, h, w = seg.shape
         _, H, W = target.shape
         d_seg = torch.empty_like(seg)
-        g = g.reshape(1).to(F32).contiguous()
-        wp = _p(ctx.weight, F32, "ce_weight") if ctx.weight is not None else _null()
-        _hip.call("cseg_ohem_bwd", _p(seg, F32, "seg"), _p(target, I64, "target"), wp, ctx.ignore_index, B, K, h, w, H, W, _pf(p), _pf(lse),
-                  _pf(out), _pf(outi), _p(g, F32, "d_loss"), _pf(d_seg), _hip.stream_ptr())
+        g = _d_loss(g)
+        _hip.call("cseg_ohem_bwd", _p(seg, F32, "seg"), _p(target, I64, "target"), _opt(ctx.weight, F32, "ce_weight"), ctx.ignore_index,
+                  B, K, h, w, H, W, _pf(p), _pf(lse), _pf(out), _pf(outi), _p(g, F32, "d_loss"), _pf(d_seg), _hip.stream_ptr())
         return d_seg, None, None, None, None, None, None, None
 
 
@@ -1318,13 +1307,6 @@ def queue_enqueue_device(keys, labels, stride, segment_queue, segment_queue_ptr,
 # ----------------------------------------------------------------------------------------------------------
 # fused (Sync)BatchNorm + residual + ReLU primitives (host logic: lib/models/tools/fused_bn.py)
 # ----------------------------------------------------------------------------------------------------------
-F64 = torch.float64
-
-
-def _opt(t, dtype, what):
-    return _p(t, dtype, what) if t is not None else _null()
-
-
 def _bn_dims(x):
     B, C = x.shape[0], x.shape[1]
     HW = 1

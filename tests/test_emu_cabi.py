@@ -144,6 +144,34 @@ def test_upsample_ce_matches_torch_and_oracle(kw, monkeypatch):
     _replay(monkeypatch, "test_gpu_kernels", "test_upsample_ce_matches_torch_and_oracle", kw)
 
 
+def test_upsample_ce_forward_without_a_status_buffer(monkeypatch):
+    """cseg_upsample_ce_fwd through the C ABI with status = NULL and a label equal to K: the bad label is dropped as it is with a status
+    buffer (the same loss, bit for bit), it is just not counted; with the buffer the count is 1 (the ignore index is not a bad label)."""
+    import ctypes
+    from contrastiveseg_amd import _hip
+    inject.install(monkeypatch)
+    B, K, h, w, H, W, ignore = 1, 3, 2, 2, 4, 4, -1
+    g = torch.Generator().manual_seed(17)
+    seg = torch.randn(B, K, h, w, generator=g)
+    target = torch.randint(0, K, (B, H, W), generator=g)
+    target[0, 1, 2] = K
+    target[0, 3, 0] = ignore
+    nb = _hip.lib().cseg_upsample_ce_blocks(B, H, W)
+
+    def forward(status):
+        partial, out, lse = torch.empty(2 * nb), torch.empty(2), torch.empty(B, H, W)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
+        _hip.call("cseg_upsample_ce_fwd", ptr(seg), ptr(target), None, ignore, B, K, h, w, H, W, ptr(partial), ptr(out), ptr(status),
+                  ptr(lse), None)
+        return out
+
+    status = torch.zeros(4, dtype=torch.int32)
+    with_status, without = forward(status), forward(None)
+    assert torch.isfinite(with_status).all() and float(with_status[1]) == H * W - 2
+    assert torch.equal(without.view(torch.int32), with_status.view(torch.int32))
+    assert status.tolist() == [0, 1, 0, 0]
+
+
 ENQ = _cases("test_gpu_kernels", "test_trainer_enqueue_on_gpu_matches_reference_golden")
 
 
