@@ -3479,3 +3479,71 @@ def augment_batch(img_u8, lab_u8, lut, params, out_hw, div_value, mean, std):
               _p(params, I32, "params"), B, Hs, Ws, Ht, Wt, float(div_value), mean3, std3, _p(out, F32, "out_img"),
               _opt(out_lab, I64, "out_lab"), _hip.stream_ptr())
     return out, out_lab
+
+
+# ----------------------------------------------------------------------------------------------------------
+# GPU data pipeline for mixed-size datasets (csrc/augment_ragged.hip); host logic: lib/datasets/tools/gpu_aug.py
+# ----------------------------------------------------------------------------------------------------------
+AUG_RAGGED_PARAM_INTS = 16
+
+
+def _ragged_records(params, offsets, dev):
+    """Host records (i32 [B,AUG_RAGGED_PARAM_INTS], i64 [B,2]) -> (host copies the library validates, their device copies)."""
+    ph = params.detach().to("cpu", I32).contiguous()
+    oh = offsets.detach().to("cpu", I64).contiguous()
+    if ph.dim() != 2 or ph.shape[1] != AUG_RAGGED_PARAM_INTS or tuple(oh.shape) != (ph.shape[0], 2):
+        raise RuntimeError("ragged records: params must be [B,%d] and offsets [B,2] (got %s, %s)"
+                           % (AUG_RAGGED_PARAM_INTS, tuple(ph.shape), tuple(oh.shape)))
+    return ph, oh, ph.to(dev, non_blocking=True), oh.to(dev, non_blocking=True)
+
+
+def _ragged_pixels(img_u8, lab_u8, what):
+    if img_u8.numel() % 3:
+        raise RuntimeError("%s: the packed image buffer must hold 3 bytes per pixel" % what)
+    n = img_u8.numel() // 3
+    if lab_u8 is not None and lab_u8.numel() != n:
+        raise RuntimeError("%s: the packed label buffer has %d pixels, the image buffer %d" % (what, lab_u8.numel(), n))
+    return n
+
+
+@torch.no_grad()
+def resize_ragged(img_u8, lab_u8, params, offsets):
+    """Stage 1 of the ragged pipeline. img_u8: packed u8 buffer of HWC images (any shape, 3 bytes per pixel), lab_u8 packed u8
+    labels or None, params i32 [B,AUG_RAGGED_PARAM_INTS] and offsets i64 [B,2] HOST tensors (include/cseg_hip.h)
+    -> (mid_img u8 [M,3], mid_lab u8 [M] or None): the intermediate images of the samples with two resamplings, M = the stage-1
+    pixels the records address (at least 1)."""
+    dev = img_u8.device
+    U8 = torch.uint8
+    n = _ragged_pixels(img_u8, lab_u8, "resize_ragged")
+    ph, oh, pd, od = _ragged_records(params, offsets, dev)
+    two = ph[:, 2] > 0
+    m = max(1, int((oh[:, 1] + ph[:, 2].long() * ph[:, 3].long())[two].max())) if bool(two.any()) else 1
+    mid_img = torch.empty(m, 3, dtype=U8, device=dev)
+    mid_lab = torch.empty(m, dtype=U8, device=dev) if lab_u8 is not None else None
+    _hip.call("cseg_resize_ragged", _p(img_u8, U8, "img"), _opt(lab_u8, U8, "labelmap"), n, _p(pd, I32, "params"),
+              _p(od, I64, "offsets"), ctypes.c_void_p(ph.data_ptr()), ctypes.c_void_p(oh.data_ptr()), ph.shape[0],
+              _p(mid_img, U8, "mid_img"), _opt(mid_lab, U8, "mid_lab"), m, _hip.stream_ptr())
+    return mid_img, mid_lab
+
+
+@torch.no_grad()
+def augment_ragged(img_u8, lab_u8, lut, params, offsets, out_hw, div_value, mean, std, mid=None):
+    """Stage 2. Arguments as resize_ragged, `mid` = its result (needed when a record has W1 > 0), lut i16 [256] or None
+    -> (img f32 [B,3,Ht,Wt], labelmap i64 [B,Ht,Wt] or None)."""
+    dev = img_u8.device
+    U8 = torch.uint8
+    Ht, Wt = out_hw
+    n = _ragged_pixels(img_u8, lab_u8, "augment_ragged")
+    ph, oh, pd, od = _ragged_records(params, offsets, dev)
+    B = ph.shape[0]
+    mid_img, mid_lab = mid if mid is not None else (None, None)
+    m = mid_img.numel() // 3 if mid_img is not None else 0
+    out = torch.empty(B, 3, Ht, Wt, dtype=F32, device=dev)
+    out_lab = torch.empty(B, Ht, Wt, dtype=I64, device=dev) if lab_u8 is not None else None
+    mean3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    std3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+    _hip.call("cseg_augment_ragged", _p(img_u8, U8, "img"), _opt(lab_u8, U8, "labelmap"), n, _opt(mid_img, U8, "mid_img"),
+              _opt(mid_lab, U8, "mid_lab"), m, _opt(lut, I16, "lut"), _p(pd, I32, "params"), _p(od, I64, "offsets"),
+              ctypes.c_void_p(ph.data_ptr()), ctypes.c_void_p(oh.data_ptr()), B, Ht, Wt, float(div_value), mean3, std3,
+              _p(out, F32, "out_img"), _opt(out_lab, I64, "out_lab"), _hip.stream_ptr())
+    return out, out_lab

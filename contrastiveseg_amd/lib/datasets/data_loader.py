@@ -7,8 +7,13 @@ raw uint8 batches to the device through pinned memory on a side HIP stream, one 
 augmentation, tensor conversion, label encoding and collation are one kernel on the GPU
 (lib/datasets/tools/gpu_aug.py -> cseg_augment_batch). Sample order: a fresh torch.randperm per epoch like the
 reference's RandomSampler; with a process group every rank takes its strided share of it (DistributedSampler semantics,
-data_loader.py:137: batch_size // world_size per rank). Images of one batch must share a size (Cityscapes does;
-mixed-size datasets are outside the accelerated path)."""
+data_loader.py:137: batch_size // world_size per rank). A batch of equal-sized images (Cityscapes) travels as one stacked array and
+takes the one-kernel path; a batch of differing sizes (COCO-Stuff, ADE20K, ...) travels as one packed buffer with the sizes beside it
+and takes the ragged path (cseg_resize_ragged + cseg_augment_ragged). Under `val.data_transformer.size_mode: diverse_size` the
+validation loader yields one image per batch at its own size, as the reference does (data_helper.py:107-112). Still outside the
+accelerated path, refused by name: the `Tester` under `diverse_size` (it needs the final resize back to the original size),
+`random_rotate` and the colour transforms (saturation, hue, contrast, perm), `size_mode` `multi_size` / `max_size`, `align_method`
+`scale_and_pad` / `only_scale`, a resampling after a crop."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -50,8 +55,17 @@ def _decode(pair, bgr):
     return np.ascontiguousarray(img), np.ascontiguousarray(lab.astype(np.uint8))
 
 
+def pack_ragged(images, labels):
+    """Images [H_b,W_b,3] u8 of differing sizes -> (one packed [N,3] u8 buffer, sample after sample in HWC order, the packed [N] u8
+    labels or None, [(W_b, H_b)]): the ragged batch of csrc/augment_ragged.hip. Pixel offsets are the running sums of W_b * H_b."""
+    img = np.concatenate([im.reshape(-1, 3) for im in images])
+    lab = np.concatenate([lb.reshape(-1) for lb in labels]) if labels is not None else None
+    return img, lab, [(im.shape[1], im.shape[0]) for im in images]
+
+
 class FolderSource(object):
-    """Raw uint8 batches from image / label files."""
+    """Raw uint8 batches from image / label files: (stacked images, stacked labels) when the images of a batch share a size,
+    (packed images, packed labels, sizes) otherwise."""
 
     def __init__(self, configer, split, batch_size, shuffle, drop_last=True, workers=8):
         self.pairs = list_pairs(configer.get('data', 'data_dir'), split)
@@ -105,9 +119,13 @@ class FolderSource(object):
         self.epoch += 1                                    # a caller that never calls set_epoch still gets a new permutation
         for i in range(0, len(order), self.batch_size):
             items = list(self.pool.map(lambda k: _decode(self.pairs[k], self.bgr), order[i:i + self.batch_size]))
-            if len({it[0].shape for it in items}) != 1:
-                raise RuntimeError('images of one batch differ in size; the accelerated loader needs a common size')
-            yield np.stack([it[0] for it in items]), np.stack([it[1] for it in items])
+            for img, lab in items:
+                if img.shape[:2] != lab.shape:
+                    raise RuntimeError('image {} and label {} of one pair differ in size'.format(img.shape[:2], lab.shape))
+            if len({it[0].shape for it in items}) == 1:
+                yield np.stack([it[0] for it in items]), np.stack([it[1] for it in items])
+            else:
+                yield pack_ragged([it[0] for it in items], [it[1] for it in items])
 
 
 class SyntheticRawSource(object):
@@ -154,9 +172,11 @@ class GPUAugLoader(object):
         return len(self.source)
 
     def _upload(self, raw):
-        img, lab = raw
+        """raw: (images, labels) stacked, or (images, labels, sizes) packed -> (device images, device labels, sizes or None, event)"""
+        img, lab = raw[0], raw[1]
+        sizes = raw[2] if len(raw) > 2 else None
         if self.device.type != 'cuda':
-            return torch.from_numpy(img), torch.from_numpy(lab), None
+            return torch.from_numpy(img), torch.from_numpy(lab), sizes, None
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=self.device)
         with torch.cuda.stream(self._stream):
@@ -164,7 +184,7 @@ class GPUAugLoader(object):
             tl = torch.from_numpy(lab).pin_memory().to(self.device, non_blocking=True)
             done = torch.cuda.Event()
             done.record(self._stream)
-        return ti, tl, done
+        return ti, tl, sizes, done
 
     def __iter__(self):
         it = iter(self.source)
@@ -173,7 +193,7 @@ class GPUAugLoader(object):
         except StopIteration:
             return
         while nxt is not None:
-            ti, tl, done = nxt
+            ti, tl, sizes, done = nxt
             try:
                 nxt = self._upload(next(it))        # overlaps the kernel + the training step of the current batch
             except StopIteration:
@@ -182,7 +202,7 @@ class GPUAugLoader(object):
                 torch.cuda.current_stream(self.device).wait_event(done)
                 ti.record_stream(torch.cuda.current_stream(self.device))
                 tl.record_stream(torch.cuda.current_stream(self.device))
-            out = self.transform(ti, tl)
+            out = self.transform(ti, tl, sizes=sizes)
             yield {'img': out['img'], 'labelmap': out['labelmap']}
 
 
@@ -234,15 +254,17 @@ class TestFolderLoader(object):
         for i in range(0, len(mine), self.batch_size):
             chunk = mine[i:i + self.batch_size]
             items = list(self.pool.map(self._decode, chunk))
-            if len({it[0].shape for it in items}) != 1:
-                raise RuntimeError('images of one batch differ in size; the accelerated loader needs a common size')
-            ti = torch.from_numpy(np.stack([it[0] for it in items])).to(self.device)
-            tl = torch.from_numpy(np.stack([it[1] for it in items])).to(self.device) if self.label_dir is not None else None
-            out = self.transform(ti, tl)
-            params = out['aug_params']
+            labels = [it[1] for it in items] if self.label_dir is not None else None
+            if len({it[0].shape for it in items}) == 1:
+                img, lab, sizes = np.stack([it[0] for it in items]), np.stack(labels) if labels is not None else None, None
+            else:                                          # mixed sizes under fix_size + only_pad: every image padded to input_size
+                img, lab, sizes = pack_ragged([it[0] for it in items], labels)
+            ti = torch.from_numpy(img).to(self.device)
+            tl = torch.from_numpy(lab).to(self.device) if lab is not None else None
+            out = self.transform(ti, tl, sizes=sizes)
             batch = {'img': out['img'], 'name': [stem for _, stem in chunk],
-                     'border_size': [(int(p[4]), int(p[5])) for p in params.tolist()],
-                     'pad_offset': [(int(p[8]), int(p[9])) for p in params.tolist()]}
+                     'border_size': [(int(w), int(h)) for w, h in out['border_size']],
+                     'pad_offset': [(int(l), int(u)) for l, u in out['pad_offset']]}
             if tl is not None:
                 batch['labelmap'] = out['labelmap']
             yield batch
@@ -265,6 +287,9 @@ class DataLoader(object):
 
     def get_valloader(self, dataset='val'):
         bs = max(1, self.configer.get('val', 'batch_size') // get_world_size())
+        dt = self.configer.get('val', 'data_transformer') if self.configer.exists('val', 'data_transformer') else {}
+        if dt.get('size_mode', 'fix_size') == 'diverse_size':
+            bs = 1                                         # every image alone at its own size (data_helper.py:107-112)
         src = FolderSource(self.configer, dataset, bs, shuffle=False, drop_last=False, workers=self._workers())
         return GPUAugLoader(self.configer, src, self.device, 'val')
 

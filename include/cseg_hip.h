@@ -735,6 +735,45 @@ int cseg_augment_batch(const uint8_t* img, const uint8_t* lab, const int16_t* lu
                        int64_t* out_lab, cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * GPU data pipeline for mixed-size datasets (csrc/augment_ragged.hip): the chain above for a RAGGED batch -- B images of
+ * differing sizes packed into one u8 buffer (HWC, sample b starts at pixel offsets[2 b]), one packed label buffer with the same
+ * pixel offsets -- and for the reference's `resize` transform (cv2_aug_transforms.py:605-651) ahead of `random_resize`: two
+ * resamplings with the intermediate image rounded to bytes, which do not collapse into one. Two stages share one record array:
+ *   cseg_resize_ragged   stage 1, only for samples with two non-identity resamplings (W1 > 0): raw -> u8 image (INTER_CUBIC, the Q11
+ *                        rule of cseg_augment_batch) AND u8 label (INTER_NEAREST) of W1 x H1 at pixel offsets[2 b + 1] of the second
+ *                        packed buffer (mid_img / mid_lab). The label is resampled here, not composed into stage 2's index map.
+ *                        Samples with W1 = 0 cost no work; when no sample has W1 > 0 nothing is launched.
+ *   cseg_augment_ragged  stage 2 = pad -> flip -> crop -> one resize -> brightness -> normalise -> LUT -> ReLabel(255,-1) into
+ *                        out_img [B,3,Ht,Wt] f32 / out_lab [B,Ht,Wt] i64; the source of sample b is its stage-1 result when W1 > 0,
+ *                        the raw buffer otherwise.
+ * A `mirror` flag of a stage reads the source columns mirrored: the stage then computes cv2.resize(cv2.flip(src, 1), ...), which
+ * is what a random_hflip AHEAD of that resampling does (it is not a flip after it).
+ * CSEG_AUG_RAGGED_PARAM_INTS int32 per sample:
+ *   [0] W0 [1] H0     size of the sample in the raw buffer
+ *   [2] W1 [3] H1     stage-1 (intermediate) size; 0 0 = stage 1 skipped, stage 2 reads the raw sample
+ *   [4] mirror1       stage 1 reads the raw columns mirrored (0/1)
+ *   [5] Wr [6] Hr     size after stage 2's resize; equal to its source size (W1 x H1, else W0 x H0) = copy, no resampling
+ *   [7] mirror2       stage 2 reads its source columns mirrored (0/1), resize or copy
+ *   [8] x_off [9] y_off   crop origin in the Wr x Hr image; [10] tw [11] th crop size (inside Wr x Hr)
+ *   [12] flip         output flip (0/1), applied to the crop
+ *   [13] shift        brightness shift (0 = skipped)
+ *   [14] left_pad [15] up_pad   collate offsets of the crop in the Ht x Wt output (image 0, label -1 around it)
+ * offsets: int64 [B][2] = {pixel offset in the raw buffer, pixel offset in the stage-1 buffer (ignored when W1 = 0)}.
+ * params / offsets are DEVICE arrays; params_host / offsets_host are the same arrays in host memory, checked before the launch
+ * (returns 0, cseg_last_error()): null pointers, B outside 1..65535, non-positive sizes, a sample that would read past src_pixels
+ * or lie past mid_pixels (buffer lengths in pixels), a crop outside its resized image, labels in without labels out.
+ * lab / mid_lab / out_lab may all be NULL (no labels); lut [256] i16 or NULL. No atomics, no LDS: deterministic.
+ * ------------------------------------------------------------------------------------------------ */
+#define CSEG_AUG_RAGGED_PARAM_INTS 16
+int cseg_resize_ragged(const uint8_t* img, const uint8_t* lab, long src_pixels, const int32_t* params, const int64_t* offsets,
+                       const int32_t* params_host, const int64_t* offsets_host, int B, uint8_t* mid_img, uint8_t* mid_lab,
+                       long mid_pixels, cseg_stream_t stream);
+int cseg_augment_ragged(const uint8_t* img, const uint8_t* lab, long src_pixels, const uint8_t* mid_img, const uint8_t* mid_lab,
+                        long mid_pixels, const int16_t* lut, const int32_t* params, const int64_t* offsets,
+                        const int32_t* params_host, const int64_t* offsets_host, int B, int Ht, int Wt, float div_value,
+                        const float* mean3, const float* std3, float* out_img, int64_t* out_lab, cseg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Test phase (csrc/ms_eval.hip).  Replaces the tensor work of segmentor/tester.py:310-327, 380-398 (ss_test / ms_test) with
  * the argmax of :189, and lib/metrics/running_score.py:_fast_hist.  No full-resolution [B,K,H,W] tensor is needed.
  *
