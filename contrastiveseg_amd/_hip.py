@@ -175,6 +175,9 @@ SIGNATURES = {
                                      _c_int, _c_float, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "cseg_ms_fuse_argmax": (_c_int, [_c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int), ctypes.POINTER(_c_int),
                                      ctypes.POINTER(_c_float)] + [_c_int] * 4 + [_ptr, _ptr, _ptr]),
+    "cseg_ms_fuse_argmax_ragged": (_c_int, [_c_int, _c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int),
+                                            ctypes.POINTER(_c_int), ctypes.POINTER(_c_float), ctypes.POINTER(_c_int), _c_int, _ptr, _ptr,
+                                            _ptr]),
     "cseg_confusion_update": (_c_int, [_ptr, _ptr, ctypes.c_long, _c_int, _c_int, _ptr, _ptr]),
     "cseg_crop_fuse_argmax": (_c_int, [_c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int)] + [_c_int] * 4 +
                               [_ptr, _ptr, _ptr]),

@@ -1,0 +1,154 @@
+// The test phase's multi-scale + flip fusion kernel, one text for its two launch shapes: MsArgs, a [B,K,H,W] batch (ms_eval.hip,
+// cseg_ms_fuse_argmax), and RgArgs, images of differing sizes with packed outputs (ms_eval_ragged.hip, cseg_ms_fuse_argmax_ragged). The
+// two differ in which image and pixel a thread owns and where its byte and its fp32 column go, which is decided at compile time; the
+// taps and the class loop are the same statements, so a pixel (y, x) of a W-wide map gets the same operations from both.
+#pragma once
+#include <type_traits>
+
+#include "cseg_taps.h"
+
+namespace {
+
+constexpr int MS_MAX_TERMS = 8;
+constexpr int MS_MAX_K = 256;
+constexpr int RG_IMAGES = 8;             // images per ragged launch: RgArgs stays under HIP's 4 KB of kernel arguments
+
+struct MsTerm {
+    const float* a;      // [B,K,h,w]
+    const float* b;      // [B,K,h,w] net output for the mirrored input, or null
+    int h, w;
+    float sy, sx, wt;
+};
+
+struct MsArgs {
+    MsTerm t[MS_MAX_TERMS];
+    int n, B, K, H, W;
+};
+
+struct RgImage {
+    long pix0;           // pixels of the images before this one in the packed outputs
+    int W;               // padded width: the geometry's, and the mirror's
+    int w;               // border width: the row length of this image's outputs
+    int npix;            // h * w of the border
+    int block0;          // first block of this image in the launch
+};
+
+struct RgArgs {          // maps of one image: [1,K,h,w]
+    MsTerm t[RG_IMAGES][MS_MAX_TERMS];
+    RgImage im[RG_IMAGES];
+    int n_images, n, K;
+};
+static_assert(sizeof(RgArgs) + 2 * sizeof(void*) <= 4096, "the argument block of the ragged launch exceeds HIP's 4 KB");
+
+// The weight of bl_tap's upper tap with its one rounding stated: fma(s, o, -i0) when FUSED, else the rounded product minus i0.
+// bl_tap itself is compiled under the default contraction, which leaves that choice to the optimiser, instance by instance.
+template <bool FUSED>
+__device__ __forceinline__ float ms_tap_weight(float s, int o, int i0) {
+#pragma clang fp contract(off)
+    return FUSED ? fmaf(s, (float)o, -(float)i0) : s * (float)o - (float)i0;
+}
+
+// Which of the two the MsArgs instances -- what cseg_ms_fuse_argmax has always run -- got from the optimiser. On the GPU: the weight
+// of the mirrored column fused in every instance; the row weight and the plain column's weight fused in the one-term instance only
+// (from two terms on the products s * y and s * x are one packed multiply, which keeps them from fusing). In a host build of this
+// text (the CPU emulation of the tests) nothing is fused.
+#if defined(__HIP_DEVICE_COMPILE__)
+template <int NT> constexpr bool MS_PLAIN_WEIGHTS_FUSED = NT == 1;
+constexpr bool MS_MIRROR_WEIGHT_FUSED = true;
+#else
+template <int NT> constexpr bool MS_PLAIN_WEIGHTS_FUSED = false;
+constexpr bool MS_MIRROR_WEIGHT_FUSED = false;
+#endif
+
+// MsArgs: one thread per output pixel of the batch. RgArgs: one thread per pixel of an image's border; image j owns the blocks from
+// im[j].block0 on, so the block-to-image map and every descriptor read are wave-uniform.
+template <int NT, class Args>
+__global__ __launch_bounds__(256) void ms_fuse_kernel(Args A, uint8_t* __restrict__ pred, float* __restrict__ fused) {
+#pragma clang fp contract(off)
+    constexpr bool ragged = std::is_same<Args, RgArgs>::value;
+    long g, HW;
+    int b, p, y, x, xm;
+    const MsTerm* t;
+    if constexpr (ragged) {
+        int img = 0;
+#pragma unroll
+        for (int j = 1; j < RG_IMAGES; ++j)
+            if (j < A.n_images && (int)blockIdx.x >= A.im[j].block0) img = j;
+        p = ((int)blockIdx.x - A.im[img].block0) * 256 + (int)threadIdx.x;
+        if (p >= A.im[img].npix) return;
+        HW = A.im[img].npix;
+        g = A.im[img].pix0 + p;
+        b = 0;
+        y = p / A.im[img].w; x = p - y * A.im[img].w;
+        xm = A.im[img].W - 1 - x;
+        t = A.t[img];
+        if (fused) fused += (size_t)A.K * (size_t)A.im[img].pix0;          // this image's [K,h,w] block
+    } else {
+        g = (long)blockIdx.x * 256 + threadIdx.x;
+        HW = (long)A.H * A.W;
+        if (g >= (long)A.B * HW) return;
+        b = (int)(g / HW);
+        p = (int)(g - (long)b * HW);
+        y = p / A.W; x = p - y * A.W;
+        xm = A.W - 1 - x;
+        t = A.t;
+    }
+
+    int r0[NT], r1[NT], xa0[NT], xa1[NT], xb0[NT], xb1[NT];
+    float ly[NT], lxa[NT], lxb[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        r0[i] = r1[i] = xa0[i] = xa1[i] = xb0[i] = xb1[i] = 0;
+        ly[i] = lxa[i] = lxb[i] = 0.f;
+        if (i < A.n) {
+            int y0, y1;
+            bl_tap(t[i].sy, t[i].h, y, y0, y1, ly[i]);
+            bl_tap(t[i].sx, t[i].w, x, xa0[i], xa1[i], lxa[i]);
+            bl_tap(t[i].sx, t[i].w, xm, xb0[i], xb1[i], lxb[i]);
+            if constexpr (ragged) {
+                // The ragged instances must give the bits of the MsArgs instances image by image, so they state the roundings of the
+                // tap weights instead of leaving them to a second, independent choice of the optimiser; the tests compare the two
+                // bit for bit, on the GPU and on the emulation (tests/test_gpu_ms_eval_ragged.py, tests/test_emu_ms_eval_ragged.py).
+                ly[i] = ms_tap_weight<MS_PLAIN_WEIGHTS_FUSED<NT>>(t[i].sy, y, y0);
+                lxa[i] = ms_tap_weight<MS_PLAIN_WEIGHTS_FUSED<NT>>(t[i].sx, x, xa0[i]);
+                lxb[i] = ms_tap_weight<MS_MIRROR_WEIGHT_FUSED>(t[i].sx, xm, xb0[i]);
+            }
+            // the fp32 source coordinate of the last output index is at most n_in - 1 + rounding, so these change no tap; they
+            // make every address provably inside the plane
+            y0 = min(y0, t[i].h - 1); y1 = min(y1, t[i].h - 1);
+            xa0[i] = min(xa0[i], t[i].w - 1); xa1[i] = min(xa1[i], t[i].w - 1);
+            xb0[i] = min(xb0[i], t[i].w - 1); xb1[i] = min(xb1[i], t[i].w - 1);
+            r0[i] = y0 * t[i].w;
+            r1[i] = y1 * t[i].w;
+        }
+    }
+
+    float best = 0.f;
+    int best_k = 0;
+    for (int k = 0; k < A.K; ++k) {
+        float v = 0.f;
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            if (i < A.n) {
+                const size_t plane = ((size_t)b * A.K + k) * ((size_t)t[i].h * t[i].w);
+                const float ly1 = ly[i], ly0 = 1.f - ly1;
+                const float* s = t[i].a + plane;
+                float c0 = ly0 * s[r0[i] + xa0[i]] + ly1 * s[r1[i] + xa0[i]];
+                float c1 = ly0 * s[r0[i] + xa1[i]] + ly1 * s[r1[i] + xa1[i]];
+                float u = fmaf(lxa[i], c1 - c0, c0);
+                if (t[i].b) {
+                    s = t[i].b + plane;
+                    c0 = ly0 * s[r0[i] + xb0[i]] + ly1 * s[r1[i] + xb0[i]];
+                    c1 = ly0 * s[r0[i] + xb1[i]] + ly1 * s[r1[i] + xb1[i]];
+                    u = u + fmaf(lxb[i], c1 - c0, c0);
+                }
+                v = v + t[i].wt * u;
+            }
+        }
+        if (fused) fused[((size_t)b * A.K + k) * HW + p] = v;
+        if (k == 0 || v > best) { best = v; best_k = k; }
+    }
+    if (pred) pred[g] = (uint8_t)best_k;
+}
+
+}  // namespace

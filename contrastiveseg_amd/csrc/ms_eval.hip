@@ -6,7 +6,8 @@
 // here none of the full-resolution tensors exists: one kernel reads the coarse maps (1/16 of the pixels each at stride 4; L1/L2
 // hits) and writes one byte per pixel.
 //
-// ms_fuse_kernel   one thread per output pixel. The taps of every term (row offsets, columns, blend factors; for the flipped map
+// ms_fuse_kernel   lives in cseg_ms_fuse.h; this file launches its MsArgs instances, ms_eval_ragged.hip the RgArgs ones.
+//                  One thread per output pixel. The taps of every term (row offsets, columns, blend factors; for the flipped map
 //                  the taps of the MIRRORED output column W-1-x, which is what flipping the upsampled map means) are computed once
 //                  with the package's fp32 index arithmetic (bl_tap) and stay in registers: the term loop is unrolled
 //                  to the template's NT. Classes run in the outer loop, terms inside, in the reference's association order
@@ -18,85 +19,11 @@
 // confusion_*      integer counts, exact. K <= 128: per-block histogram of K*K 32-bit bins in LDS, non-zero bins flushed with one
 //                  64-bit global atomic per bin and block. Above: lanes that hold runs of equal (gt, pred) pairs -- neighbouring
 //                  pixels mostly do -- are merged with a segmented scan over the wave, one global atomic per run.
-#include "cseg_taps.h"
+#include "cseg_ms_fuse.h"        // ms_fuse_kernel, shared with ms_eval_ragged.hip
 
 namespace {
 
-constexpr int MS_MAX_TERMS = 8;
-constexpr int MS_MAX_K = 256;
 constexpr int CONF_LDS_K = 128;          // K*K*4 bytes of LDS: 64 KB at 128
-
-struct MsTerm {
-    const float* a;      // [B,K,h,w]
-    const float* b;      // [B,K,h,w] net output for the mirrored input, or null
-    int h, w;
-    float sy, sx, wt;
-};
-
-struct MsArgs {
-    MsTerm t[MS_MAX_TERMS];
-    int n, B, K, H, W;
-};
-
-template <int NT>
-__global__ __launch_bounds__(256) void ms_fuse_kernel(MsArgs A, uint8_t* __restrict__ pred, float* __restrict__ fused) {
-#pragma clang fp contract(off)
-    const long g = (long)blockIdx.x * 256 + threadIdx.x;
-    const long HW = (long)A.H * A.W;
-    if (g >= (long)A.B * HW) return;
-    const int b = (int)(g / HW);
-    const int p = (int)(g - (long)b * HW);
-    const int y = p / A.W, x = p - y * A.W;
-    const int xm = A.W - 1 - x;
-
-    int r0[NT], r1[NT], xa0[NT], xa1[NT], xb0[NT], xb1[NT];
-    float ly[NT], lxa[NT], lxb[NT];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        r0[i] = r1[i] = xa0[i] = xa1[i] = xb0[i] = xb1[i] = 0;
-        ly[i] = lxa[i] = lxb[i] = 0.f;
-        if (i < A.n) {
-            int y0, y1;
-            bl_tap(A.t[i].sy, A.t[i].h, y, y0, y1, ly[i]);
-            bl_tap(A.t[i].sx, A.t[i].w, x, xa0[i], xa1[i], lxa[i]);
-            bl_tap(A.t[i].sx, A.t[i].w, xm, xb0[i], xb1[i], lxb[i]);
-            // the fp32 source coordinate of the last output index is at most n_in - 1 + rounding, so these change no tap; they
-            // make every address provably inside the plane
-            y0 = min(y0, A.t[i].h - 1); y1 = min(y1, A.t[i].h - 1);
-            xa0[i] = min(xa0[i], A.t[i].w - 1); xa1[i] = min(xa1[i], A.t[i].w - 1);
-            xb0[i] = min(xb0[i], A.t[i].w - 1); xb1[i] = min(xb1[i], A.t[i].w - 1);
-            r0[i] = y0 * A.t[i].w;
-            r1[i] = y1 * A.t[i].w;
-        }
-    }
-
-    float best = 0.f;
-    int best_k = 0;
-    for (int k = 0; k < A.K; ++k) {
-        float v = 0.f;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            if (i < A.n) {
-                const size_t plane = ((size_t)b * A.K + k) * ((size_t)A.t[i].h * A.t[i].w);
-                const float ly1 = ly[i], ly0 = 1.f - ly1;
-                const float* s = A.t[i].a + plane;
-                float c0 = ly0 * s[r0[i] + xa0[i]] + ly1 * s[r1[i] + xa0[i]];
-                float c1 = ly0 * s[r0[i] + xa1[i]] + ly1 * s[r1[i] + xa1[i]];
-                float u = fmaf(lxa[i], c1 - c0, c0);
-                if (A.t[i].b) {
-                    s = A.t[i].b + plane;
-                    c0 = ly0 * s[r0[i] + xb0[i]] + ly1 * s[r1[i] + xb0[i]];
-                    c1 = ly0 * s[r0[i] + xb1[i]] + ly1 * s[r1[i] + xb1[i]];
-                    u = u + fmaf(lxb[i], c1 - c0, c0);
-                }
-                v = v + A.t[i].wt * u;
-            }
-        }
-        if (fused) fused[((size_t)b * A.K + k) * HW + p] = v;
-        if (k == 0 || v > best) { best = v; best_k = k; }
-    }
-    if (pred) pred[g] = (uint8_t)best_k;
-}
 
 // bin of one pixel under RunningScore._fast_hist's mask, or -1
 __device__ __forceinline__ int conf_bin(const uint8_t* pred, const int64_t* target, long i, int K, int ignore_index) {
@@ -178,7 +105,7 @@ extern "C" int cseg_ms_fuse_argmax(int n_terms, const float* const* plain, const
         t.wt = weights[i];
     }
     const unsigned blocks = (unsigned)(((long)B * H * W + 255) / 256);
-#define LAUNCH(NT) hipLaunchKernelGGL(ms_fuse_kernel<NT>, dim3(blocks), dim3(256), 0, stream, A, pred, fused)
+#define LAUNCH(NT) hipLaunchKernelGGL((ms_fuse_kernel<NT, MsArgs>), dim3(blocks), dim3(256), 0, stream, A, pred, fused)
     if (n_terms <= 1) LAUNCH(1);
     else if (n_terms <= 2) LAUNCH(2);
     else if (n_terms <= 4) LAUNCH(4);

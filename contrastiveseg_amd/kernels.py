@@ -1,6 +1,7 @@
 """Thin autograd wrappers over the C-ABI (contrastiveseg_amd/_hip.py). Same pattern as the reference's own native
 ops (lib/extensions/cc_attention/functions.py:20-47): a torch.autograd.Function that pre-allocates outputs, passes
 raw pointers + the current stream, and raises RuntimeError on a 0 return. No CPU path."""
+import collections
 import ctypes
 
 import os
@@ -1151,6 +1152,67 @@ def ms_fuse_argmax(terms, H, W, want_fused=False, want_pred=True):
     _hip.call("cseg_ms_fuse_argmax", n, pa, pb, hs, ws, wt, B, K, int(H), int(W), _pf(pred) if want_pred else _null(),
               _pf(fused) if want_fused else _null(), _hip.stream_ptr())
     return (pred, fused) if want_fused else pred
+
+
+RaggedScores = collections.namedtuple("RaggedScores", ["pred", "preds", "fused", "fuseds"])
+
+
+@torch.no_grad()
+def ms_fuse_argmax_ragged(images, want_fused=False, want_pred=True):
+    """ms_fuse_argmax for a batch of images of differing sizes, the list branches of segmentor/tester.py:328-341, 400-421 with the crop
+    and argmax of :169-189 (csrc/ms_eval_ragged.hip). `images` is a list of (terms, (Hp, Wp), (h, w)): terms as in ms_fuse_argmax with
+    maps [1,K,hc,wc], (Hp, Wp) the padded size whose geometry the upsampling and the mirror take, (h, w) the border, the unpadded
+    top-left region, which alone is computed. Every image has the same K and the same number of terms.
+    -> RaggedScores(pred, preds, fused, fuseds): pred the packed u8 buffer [sum h*w] (the images one after the other, each row-major)
+    and preds its per-image [h,w] views; fused the packed fp32 buffer [K * sum h*w] (image-major, then [K,h,w]) and fuseds its
+    per-image [K,h,w] views. A pair that was not asked for is (None, None)."""
+    n_img = len(images)
+    if n_img < 1:
+        raise RuntimeError("ms_fuse_argmax_ragged: images is empty")
+    n = len(images[0][0])
+    if n < 1 or n > MS_MAX_TERMS:
+        raise RuntimeError("ms_fuse_argmax_ragged: %d terms (1 to %d are supported)" % (n, MS_MAX_TERMS))
+    K = images[0][0][0][0].shape[1]
+    dev = images[0][0][0][0].device
+    keep, pa, pb = [], (ctypes.c_void_p * (n_img * n))(), (ctypes.c_void_p * (n_img * n))()
+    hs, ws, wt = (ctypes.c_int * (n_img * n))(), (ctypes.c_int * (n_img * n))(), (ctypes.c_float * (n_img * n))()
+    geo = (ctypes.c_int * (4 * n_img))()
+    sizes = []
+    for j, (terms, padded, border) in enumerate(images):
+        if len(terms) != n:
+            raise RuntimeError("ms_fuse_argmax_ragged: images[%d] has %d terms, images[0] has %d" % (j, len(terms), n))
+        geo[4 * j:4 * j + 4] = [int(padded[0]), int(padded[1]), int(border[0]), int(border[1])]
+        sizes.append((int(border[0]), int(border[1])))
+        for i, (a, b, w) in enumerate(terms):
+            if a.dim() != 4 or a.shape[0] != 1 or a.shape[1] != K:
+                raise RuntimeError("ms_fuse_argmax_ragged: term %d of images[%d] is %s, expected [1, %d, h, w] (K of images[0])"
+                                   % (i, j, tuple(a.shape), K))
+            e = j * n + i
+            a = a.contiguous()
+            pa[e] = _p(a, F32, "plain map").value
+            keep.append(a)
+            if b is not None:
+                if b.shape != a.shape:
+                    raise RuntimeError("ms_fuse_argmax_ragged: the flipped map of term %d of images[%d] is %s, its plain map %s"
+                                       % (i, j, tuple(b.shape), tuple(a.shape)))
+                b = b.contiguous()
+                pb[e] = _p(b, F32, "flipped map").value
+                keep.append(b)
+            hs[e], ws[e], wt[e] = a.shape[2], a.shape[3], float(w)
+    total = sum(max(h, 0) * max(w, 0) for h, w in sizes)
+    # (an empty geometry is the library's to refuse: it gets real pointers to say so)
+    pred = torch.empty(max(total, 1), dtype=U8, device=dev)[:total] if want_pred else None
+    fused = torch.empty(max(K * total, 1), dtype=F32, device=dev)[:K * total] if want_fused else None
+    _hip.call("cseg_ms_fuse_argmax_ragged", n_img, n, pa, pb, hs, ws, wt, geo, K, _pf(pred) if want_pred else _null(),
+              _pf(fused) if want_fused else _null(), _hip.stream_ptr())
+    preds, fuseds, off = [], [], 0
+    for h, w in sizes:
+        if want_pred:
+            preds.append(pred[off:off + h * w].view(h, w))
+        if want_fused:
+            fuseds.append(fused[K * off:K * (off + h * w)].view(K, h, w))
+        off += h * w
+    return RaggedScores(pred, preds if want_pred else None, fused, fuseds if want_fused else None)
 
 
 CROP_TERM_INTS = 7        # CSEG_CROP_TERM_INTS

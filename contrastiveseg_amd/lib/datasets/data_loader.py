@@ -10,9 +10,10 @@ reference's RandomSampler; with a process group every rank takes its strided sha
 data_loader.py:137: batch_size // world_size per rank). A batch of equal-sized images (Cityscapes) travels as one stacked array and
 takes the one-kernel path; a batch of differing sizes (COCO-Stuff, ADE20K, ...) travels as one packed buffer with the sizes beside it
 and takes the ragged path (cseg_resize_ragged + cseg_augment_ragged). Under `val.data_transformer.size_mode: diverse_size` the
-validation loader yields one image per batch at its own size, as the reference does (data_helper.py:107-112). Still outside the
-accelerated path, refused by name: the `Tester` under `diverse_size` (it needs the final resize back to the original size),
-`random_rotate` and the colour transforms (saturation, hue, contrast, perm), `size_mode` `multi_size` / `max_size`, `align_method`
+validation loader yields one image per batch at its own size, as the reference does (data_helper.py:107-112); under
+`test.data_transformer.size_mode: diverse_size` the test loader yields LIST batches of up to test.batch_size images, each at its own
+size padded right / down to fit_stride (collate.py:39-41, 61-68 with stack=False). Still outside the accelerated path, refused by
+name: `random_rotate` and the colour transforms (saturation, hue, contrast, perm), `size_mode` `multi_size` / `max_size`, `align_method`
 `scale_and_pad` / `only_scale`, a resampling after a crop."""
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -211,7 +212,8 @@ class TestFolderLoader(object):
     files exist, 'labelmap': i64 [B,H,W] (-1 = ignore, the collate padding included)} for the test phase (the reference's
     get_testloader, lib/datasets/data_loader.py:205-240, yields names and metas the same way). No shuffling, no dropped or
     repeated samples: with a process group every rank takes its strided share, so that the reduced confusion matrix counts every
-    image once."""
+    image once. Under size_mode diverse_size 'img' is a list of [1,3,Hp_b,Wp_b] tensors and 'labelmap' a list of [1,Hp_b,Wp_b], every
+    image at its own size padded to fit_stride (image 0, label -1), each through the transform alone as the reference collates it."""
 
     def __init__(self, configer, image_dir, label_dir, batch_size, device, workers=8):
         self.device = device
@@ -249,12 +251,30 @@ class TestFolderLoader(object):
             lab = np.ascontiguousarray(lab.astype(np.uint8))
         return np.ascontiguousarray(img), lab
 
+    def _list_batch(self, chunk, items):
+        batch = {'img': [], 'name': [stem for _, stem in chunk], 'border_size': [], 'pad_offset': []}
+        if self.label_dir is not None:
+            batch['labelmap'] = []
+        for img, lab in items:
+            ti = torch.from_numpy(img[None]).to(self.device)
+            tl = torch.from_numpy(lab[None]).to(self.device) if lab is not None else None
+            out = self.transform(ti, tl)
+            batch['img'].append(out['img'])
+            batch['border_size'].append((int(out['border_size'][0][0]), int(out['border_size'][0][1])))
+            batch['pad_offset'].append((int(out['pad_offset'][0][0]), int(out['pad_offset'][0][1])))
+            if tl is not None:
+                batch['labelmap'].append(out['labelmap'])
+        return batch
+
     def __iter__(self):
         mine = self._mine()
         for i in range(0, len(mine), self.batch_size):
             chunk = mine[i:i + self.batch_size]
             items = list(self.pool.map(self._decode, chunk))
             labels = [it[1] for it in items] if self.label_dir is not None else None
+            if self.transform.size_mode == 'diverse_size':
+                yield self._list_batch(chunk, items)
+                continue
             if len({it[0].shape for it in items}) == 1:
                 img, lab, sizes = np.stack([it[0] for it in items]), np.stack(labels) if labels is not None else None, None
             else:                                          # mixed sizes under fix_size + only_pad: every image padded to input_size

@@ -797,6 +797,27 @@ int cseg_confusion_update(const uint8_t* pred, const int64_t* target, long N, in
                           cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Test phase on images of differing sizes (csrc/ms_eval_ragged.hip).  Replaces the list branches of segmentor/tester.py:328-341,
+ * 400-421 (every image alone, padded right / down to fit_stride, outputs interpolated back to the PADDED size) with the top-left crop
+ * [:border_h, :border_w] and the argmax of :169-189, for a whole batch in one launch per 8 images.
+ *
+ * n_images (1..65535) images of n_terms (1..8) terms each; all arrays are HOST arrays, copied into the kernel's argument block.
+ *   geometry [n_images][4] = {Hp, Wp, h, w}: the padded size and the border (the unpadded region, top-left), 0 < h <= Hp, 0 < w <= Wp
+ *   plain, flipped, hs, ws, weights: [n_images * n_terms], image-major; entry b * n_terms + i describes term i of image b as in
+ *   cseg_ms_fuse_argmax with B = 1: plain [1,K,hs,ws] f32, flipped the same shape or NULL (`flipped` itself may be NULL).
+ * Per image b, pixel y < h, x < w and class, in this order:  v = 0;  v = v + weights * (U(plain)[y,x] + U(flipped)[y,Wp-1-x])  where U
+ * is bilinear(align_corners=True) to Hp x Wp: the geometry and the mirror are the PADDED map's, only the border is computed, and it
+ * carries the bits cseg_ms_fuse_argmax writes there for that image at H = Hp, W = Wp.
+ *   pred   packed u8 [sum_b h*w]: the images one after the other, each h x w row-major; first index among equal maxima; or NULL
+ *   fused  packed f32 [K * sum_b h*w]: image-major, then [K,h,w] (image b starts at K * (pixels of the images before it)); or NULL
+ * Not both NULL.  K <= 256; sum_b h*w and K times it below 2^31.  Deterministic (no atomics).  Nothing is launched when an argument is
+ * refused.
+ * ------------------------------------------------------------------------------------------------ */
+int cseg_ms_fuse_argmax_ragged(int n_images, int n_terms, const float* const* plain, const float* const* flipped, const int* hs,
+                               const int* ws, const float* weights, const int* geometry, int K, uint8_t* pred, float* fused,
+                               cseg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Test phase, sliding crops (csrc/crop_eval.hip).  Replaces the tensor work of segmentor/tester.py:351-378, 505-523 (sscrop_test /
  * mscrop_test) with the argmax of :189.  Neither the [B,K,hs,ws] logits canvas nor the count canvas nor a [B,K,H,W] tensor is needed.
  *
