@@ -170,14 +170,22 @@ SIGNATURES = {
     "cseg_amax_batch": (_c_int, [_ptr, _c_int, _c_int, _ptr]),
     "cseg_split_pack_batch": (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr]),
     "cseg_augment_batch": (_c_int, [_ptr, _ptr, _ptr, _ptr] + [_c_int] * 5 + [_c_float, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "cseg_augment_batch_swap": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr] + [_c_int] * 5 + [_c_float, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "cseg_resize_ragged": (_c_int, [_ptr, _ptr, ctypes.c_long, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, ctypes.c_long, _ptr]),
     "cseg_augment_ragged": (_c_int, [_ptr, _ptr, ctypes.c_long, _ptr, _ptr, ctypes.c_long, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int,
                                      _c_int, _c_float, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "cseg_augment_ragged_swap": (_c_int, [_ptr, _ptr, ctypes.c_long, _ptr, _ptr, ctypes.c_long, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int,
+                                          _c_int, _c_int, _c_float, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "cseg_ms_fuse_argmax": (_c_int, [_c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int), ctypes.POINTER(_c_int),
                                      ctypes.POINTER(_c_float)] + [_c_int] * 4 + [_ptr, _ptr, _ptr]),
     "cseg_ms_fuse_argmax_ragged": (_c_int, [_c_int, _c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int),
                                             ctypes.POINTER(_c_int), ctypes.POINTER(_c_float), ctypes.POINTER(_c_int), _c_int, _ptr, _ptr,
                                             _ptr]),
+    "cseg_ms_fuse_argmax_perm": (_c_int, [_c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int),
+                                          ctypes.POINTER(_c_int), ctypes.POINTER(_c_float), _ptr] + [_c_int] * 4 + [_ptr, _ptr, _ptr]),
+    "cseg_ms_fuse_argmax_ragged_perm": (_c_int, [_c_int, _c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int),
+                                                 ctypes.POINTER(_c_int), ctypes.POINTER(_c_float), _ptr, ctypes.POINTER(_c_int), _c_int,
+                                                 _ptr, _ptr, _ptr]),
     "cseg_confusion_update": (_c_int, [_ptr, _ptr, ctypes.c_long, _c_int, _c_int, _ptr, _ptr]),
     "cseg_crop_fuse_argmax": (_c_int, [_c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int)] + [_c_int] * 4 +
                               [_ptr, _ptr, _ptr]),

@@ -30,8 +30,9 @@ struct AugDims {
 };
 
 __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ lab,
-                                                      const int16_t* __restrict__ lut, const int32_t* __restrict__ params,
-                                                      AugDims d, float* __restrict__ out_img,
+                                                      const int16_t* __restrict__ lut,
+                                                      const int16_t* __restrict__ lut_mirrored,
+                                                      const int32_t* __restrict__ params, AugDims d, float* __restrict__ out_img,
                                                       int64_t* __restrict__ out_lab) {
     const int b = blockIdx.z;
     const int X = blockIdx.x * 64 + (threadIdx.x & 63), Y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -91,16 +92,20 @@ __global__ __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict_
         o[c * plane] = (t / d.div - d.mean[c]) / d.std[c];
     }
     if (ol) {
-        const int t = lut ? (int)lut[ls] : ls;
+        // RandomHFlip.swap_pair (cv2_aug_transforms.py:151-162): a flipped sample trades its left / right ids. A value map commutes
+        // with the nearest resampling, the crop and the padding, so it is a second table (lut o swap) picked by the flip bit.
+        const int16_t* table = (flip && lut_mirrored) ? lut_mirrored : lut;
+        const int t = table ? (int)table[ls] : ls;
         *ol = (t == 255) ? -1 : (int64_t)t;                                    // ReLabel(255, -1)
     }
 }
 
 }  // namespace
 
-extern "C" int cseg_augment_batch(const uint8_t* img, const uint8_t* lab, const int16_t* lut, const int32_t* params, int B,
-                                  int Hs, int Ws, int Ht, int Wt, float div_value, const float* mean3, const float* std3,
-                                  float* out_img, int64_t* out_lab, cseg_stream_t stream_) {
+extern "C" int cseg_augment_batch_swap(const uint8_t* img, const uint8_t* lab, const int16_t* lut, const int16_t* lut_mirrored,
+                                       const int32_t* params, int B, int Hs, int Ws, int Ht, int Wt, float div_value,
+                                       const float* mean3, const float* std3, float* out_img, int64_t* out_lab,
+                                       cseg_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     CSEG_REQUIRE(img && params && out_img && mean3 && std3, "augment_batch: null pointer");
     CSEG_REQUIRE((lab == nullptr) == (out_lab == nullptr), "augment_batch: label input and output must come together");
@@ -110,7 +115,15 @@ extern "C" int cseg_augment_batch(const uint8_t* img, const uint8_t* lab, const 
     d.B = B; d.Hs = Hs; d.Ws = Ws; d.Ht = Ht; d.Wt = Wt; d.div = div_value;
     for (int c = 0; c < 3; ++c) { d.mean[c] = mean3[c]; d.std[c] = std3[c]; }
     dim3 grid((Wt + 63) / 64, (Ht + 3) / 4, B);
-    hipLaunchKernelGGL(augment_kernel, grid, dim3(256), 0, stream, img, lab, lut, params, d, out_img, out_lab);
+    hipLaunchKernelGGL(augment_kernel, grid, dim3(256), 0, stream, img, lab, lut, lut_mirrored, params, d, out_img,
+                       out_lab);
     CSEG_CHECK_LAUNCH("augment_kernel");
     return 1;
+}
+
+extern "C" int cseg_augment_batch(const uint8_t* img, const uint8_t* lab, const int16_t* lut, const int32_t* params, int B,
+                                  int Hs, int Ws, int Ht, int Wt, float div_value, const float* mean3, const float* std3,
+                                  float* out_img, int64_t* out_lab, cseg_stream_t stream_) {
+    return cseg_augment_batch_swap(img, lab, lut, nullptr, params, B, Hs, Ws, Ht, Wt, div_value, mean3, std3, out_img, out_lab,
+                                   stream_);
 }

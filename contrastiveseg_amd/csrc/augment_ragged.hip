@@ -94,7 +94,9 @@ __global__ __launch_bounds__(256) void resize_ragged_kernel(const uint8_t* __res
 
 __global__ __launch_bounds__(256) void augment_ragged_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ lab,
                                                              const uint8_t* __restrict__ mid_img, const uint8_t* __restrict__ mid_lab,
-                                                             const int16_t* __restrict__ lut, const int32_t* __restrict__ params,
+                                                             const int16_t* __restrict__ lut,
+                                                             const int16_t* __restrict__ lut_mirrored,
+                                                             const int32_t* __restrict__ params,
                                                              const int64_t* __restrict__ offsets, RaggedDims d,
                                                              float* __restrict__ out_img, int64_t* __restrict__ out_lab) {
     const int b = blockIdx.z;
@@ -129,7 +131,10 @@ __global__ __launch_bounds__(256) void augment_ragged_kernel(const uint8_t* __re
         o[c * plane] = (t / d.div - d.mean[c]) / d.std[c];
     }
     if (ol) {
-        const int t = lut ? (int)lut[ls] : ls;
+        // RandomHFlip.swap_pair: the label is swapped iff the sample went through an odd number of flips -- the two stage mirrors
+        // and the output flip (the mirrored crop window leaves the flip pending, so it does not count). Stage 1 keeps raw ids.
+        const int16_t* table = (((p[4] ^ mirror ^ flip) & 1) && lut_mirrored) ? lut_mirrored : lut;
+        const int t = table ? (int)table[ls] : ls;
         *ol = (t == 255) ? -1 : (int64_t)t;                                    // ReLabel(255, -1)
     }
 }
@@ -183,11 +188,11 @@ extern "C" int cseg_resize_ragged(const uint8_t* img, const uint8_t* lab, long s
     return 1;
 }
 
-extern "C" int cseg_augment_ragged(const uint8_t* img, const uint8_t* lab, long src_pixels, const uint8_t* mid_img,
-                                   const uint8_t* mid_lab, long mid_pixels, const int16_t* lut, const int32_t* params,
-                                   const int64_t* offsets, const int32_t* params_host, const int64_t* offsets_host, int B, int Ht,
-                                   int Wt, float div_value, const float* mean3, const float* std3, float* out_img, int64_t* out_lab,
-                                   cseg_stream_t stream_) {
+extern "C" int cseg_augment_ragged_swap(const uint8_t* img, const uint8_t* lab, long src_pixels, const uint8_t* mid_img,
+                                        const uint8_t* mid_lab, long mid_pixels, const int16_t* lut, const int16_t* lut_mirrored,
+                                        const int32_t* params, const int64_t* offsets, const int32_t* params_host,
+                                        const int64_t* offsets_host, int B, int Ht, int Wt, float div_value, const float* mean3,
+                                        const float* std3, float* out_img, int64_t* out_lab, cseg_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     CSEG_REQUIRE(img && params && offsets && params_host && offsets_host && out_img && mean3 && std3, "augment_ragged: null pointer");
     CSEG_REQUIRE((lab == nullptr) == (out_lab == nullptr), "augment_ragged: label input and output must come together");
@@ -202,8 +207,17 @@ extern "C" int cseg_augment_ragged(const uint8_t* img, const uint8_t* lab, long 
     d.B = B; d.Ht = Ht; d.Wt = Wt; d.div = div_value;
     for (int c = 0; c < 3; ++c) { d.mean[c] = mean3[c]; d.std[c] = std3[c]; }
     dim3 grid((Wt + 63) / 64, (Ht + 3) / 4, B);
-    hipLaunchKernelGGL(augment_ragged_kernel, grid, dim3(256), 0, stream, img, lab, mid_img, mid_lab, lut, params, offsets, d, out_img,
-                       out_lab);
+    hipLaunchKernelGGL(augment_ragged_kernel, grid, dim3(256), 0, stream, img, lab, mid_img, mid_lab, lut, lut_mirrored, params, offsets, d,
+                       out_img, out_lab);
     CSEG_CHECK_LAUNCH("augment_ragged_kernel");
     return 1;
+}
+
+extern "C" int cseg_augment_ragged(const uint8_t* img, const uint8_t* lab, long src_pixels, const uint8_t* mid_img,
+                                   const uint8_t* mid_lab, long mid_pixels, const int16_t* lut, const int32_t* params,
+                                   const int64_t* offsets, const int32_t* params_host, const int64_t* offsets_host, int B, int Ht,
+                                   int Wt, float div_value, const float* mean3, const float* std3, float* out_img, int64_t* out_lab,
+                                   cseg_stream_t stream_) {
+    return cseg_augment_ragged_swap(img, lab, src_pixels, mid_img, mid_lab, mid_pixels, lut, nullptr, params, offsets, params_host,
+                                    offsets_host, B, Ht, Wt, div_value, mean3, std3, out_img, out_lab, stream_);
 }

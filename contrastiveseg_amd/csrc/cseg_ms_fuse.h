@@ -40,6 +40,38 @@ struct RgArgs {          // maps of one image: [1,K,h,w]
 };
 static_assert(sizeof(RgArgs) + 2 * sizeof(void*) <= 4096, "the argument block of the ragged launch exceeds HIP's 4 KB");
 
+// The channel permutation of the mirrored operand (left/right classes under a flip; cseg_ms_fuse_argmax_perm, _ragged_perm): output
+// class k reads class perm[k] of every flipped map. The table travels in the argument block behind the descriptors, one byte per
+// class packed into dwords, so that the class loop's look-up is a scalar dword load and a shift, both wave-uniform. An argument
+// block WITH a table is its own type: the instances of MsArgs and RgArgs themselves compile from the text they always had.
+struct MsPerm {
+    uint32_t w[MS_MAX_K / 4];
+    void fill(const uint8_t* perm, int K) {              // host: the K entries, zeros behind them
+        for (int j = 0; j < MS_MAX_K / 4; ++j) w[j] = 0u;
+        for (int k = 0; k < K; ++k) w[k >> 2] |= (uint32_t)perm[k] << ((k & 3) * 8);
+    }
+    __device__ __forceinline__ int get(int k) const { return (int)((w[k >> 2] >> ((k & 3) * 8)) & 255u); }
+};
+template <class Base>
+struct MsPermuted : Base {
+    MsPerm perm;
+};
+template <class Args> struct ms_is_permuted : std::false_type {};
+template <class Base> struct ms_is_permuted<MsPermuted<Base>> : std::true_type {};
+static_assert(sizeof(MsPermuted<RgArgs>) + 2 * sizeof(void*) <= 4096, "the permuted ragged argument block exceeds HIP's 4 KB");
+
+// perm[0..K) must be a permutation of 0..K-1. -> null, or what is wrong with it (entry index and value in *at, *val).
+inline const char* ms_perm_fault(const uint8_t* perm, int K, int* at, int* val) {
+    bool seen[MS_MAX_K] = {};
+    for (int k = 0; k < K; ++k) {
+        *at = k; *val = perm[k];
+        if (perm[k] >= K) return "is not a class";
+        if (seen[perm[k]]) return "repeats an earlier entry (not a permutation)";
+        seen[perm[k]] = true;
+    }
+    return nullptr;
+}
+
 // The weight of bl_tap's upper tap with its one rounding stated: fma(s, o, -i0) when FUSED, else the rounded product minus i0.
 // bl_tap itself is compiled under the default contraction, which leaves that choice to the optimiser, instance by instance.
 template <bool FUSED>
@@ -61,11 +93,13 @@ constexpr bool MS_MIRROR_WEIGHT_FUSED = false;
 #endif
 
 // MsArgs: one thread per output pixel of the batch. RgArgs: one thread per pixel of an image's border; image j owns the blocks from
-// im[j].block0 on, so the block-to-image map and every descriptor read are wave-uniform.
+// im[j].block0 on, so the block-to-image map and every descriptor read are wave-uniform. MsPermuted<MsArgs>, MsPermuted<RgArgs>: the
+// same two with the flipped maps' classes permuted (a compile-time property of the argument type).
 template <int NT, class Args>
 __global__ __launch_bounds__(256) void ms_fuse_kernel(Args A, uint8_t* __restrict__ pred, float* __restrict__ fused) {
 #pragma clang fp contract(off)
-    constexpr bool ragged = std::is_same<Args, RgArgs>::value;
+    constexpr bool ragged = std::is_base_of<RgArgs, Args>::value;
+    constexpr bool permuted = ms_is_permuted<Args>::value;
     long g, HW;
     int b, p, y, x, xm;
     const MsTerm* t;
@@ -105,10 +139,12 @@ __global__ __launch_bounds__(256) void ms_fuse_kernel(Args A, uint8_t* __restric
             bl_tap(t[i].sy, t[i].h, y, y0, y1, ly[i]);
             bl_tap(t[i].sx, t[i].w, x, xa0[i], xa1[i], lxa[i]);
             bl_tap(t[i].sx, t[i].w, xm, xb0[i], xb1[i], lxb[i]);
-            if constexpr (ragged) {
-                // The ragged instances must give the bits of the MsArgs instances image by image, so they state the roundings of the
-                // tap weights instead of leaving them to a second, independent choice of the optimiser; the tests compare the two
-                // bit for bit, on the GPU and on the emulation (tests/test_gpu_ms_eval_ragged.py, tests/test_emu_ms_eval_ragged.py).
+            if constexpr (ragged || permuted) {
+                // The ragged and the permuted instances must give the bits of the MsArgs instances image by image, so they state the
+                // roundings of the tap weights instead of leaving them to a second, independent choice of the optimiser; the tests
+                // compare the two bit for bit, on the GPU and on the emulation (tests/test_gpu_ms_eval_ragged.py,
+                // tests/test_emu_ms_eval_ragged.py; the permuted ones against the plain call on gathered maps,
+                // tests/test_gpu_lip_swap.py).
                 ly[i] = ms_tap_weight<MS_PLAIN_WEIGHTS_FUSED<NT>>(t[i].sy, y, y0);
                 lxa[i] = ms_tap_weight<MS_PLAIN_WEIGHTS_FUSED<NT>>(t[i].sx, x, xa0[i]);
                 lxb[i] = ms_tap_weight<MS_MIRROR_WEIGHT_FUSED>(t[i].sx, xm, xb0[i]);
@@ -137,7 +173,10 @@ __global__ __launch_bounds__(256) void ms_fuse_kernel(Args A, uint8_t* __restric
                 float c1 = ly0 * s[r0[i] + xa1[i]] + ly1 * s[r1[i] + xa1[i]];
                 float u = fmaf(lxa[i], c1 - c0, c0);
                 if (t[i].b) {
-                    s = t[i].b + plane;
+                    if constexpr (permuted)     // output class k reads class perm[k] of the mirrored operand
+                        s = t[i].b + ((size_t)b * A.K + A.perm.get(k)) * ((size_t)t[i].h * t[i].w);
+                    else
+                        s = t[i].b + plane;
                     c0 = ly0 * s[r0[i] + xb0[i]] + ly1 * s[r1[i] + xb0[i]];
                     c1 = ly0 * s[r0[i] + xb1[i]] + ly1 * s[r1[i] + xb1[i]];
                     u = u + fmaf(lxb[i], c1 - c0, c0);

@@ -16,6 +16,9 @@
 //                  maxima (torch.argmax / np.argmax). U blends vertically first, then one fused multiply-add across the columns;
 //                  floating-point contraction is switched off in the kernel so that every other rounding is where the source
 //                  puts it, on the GPU and on the emulated device alike. No atomics: deterministic.
+//                  cseg_ms_fuse_argmax_perm: the flipped map's term becomes U(b_i)[perm[k]][y,W-1-x] -- the classes that trade places
+//                  under a mirror (left / right arm of a human-parsing set) are read from their partner's channel; instances of
+//                  their own (MsPermuted<MsArgs>), so the ones without a table compile from unchanged text.
 // confusion_*      integer counts, exact. K <= 128: per-block histogram of K*K 32-bit bins in LDS, non-zero bins flushed with one
 //                  64-bit global atomic per bin and block. Above: lanes that hold runs of equal (gt, pred) pairs -- neighbouring
 //                  pixels mostly do -- are merged with a segmented scan over the wave, one global atomic per run.
@@ -79,9 +82,9 @@ __global__ __launch_bounds__(256) void confusion_global_kernel(const uint8_t* __
 
 }  // namespace
 
-extern "C" int cseg_ms_fuse_argmax(int n_terms, const float* const* plain, const float* const* flipped, const int* hs,
-                                   const int* ws, const float* weights, int B, int K, int H, int W, uint8_t* pred,
-                                   float* fused, cseg_stream_t stream_) {
+extern "C" int cseg_ms_fuse_argmax_perm(int n_terms, const float* const* plain, const float* const* flipped, const int* hs,
+                                        const int* ws, const float* weights, const uint8_t* perm, int B, int K, int H, int W,
+                                        uint8_t* pred, float* fused, cseg_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     CSEG_REQUIRE(n_terms >= 1 && n_terms <= MS_MAX_TERMS, "ms_fuse_argmax: %d terms (1 to %d are supported)", n_terms, MS_MAX_TERMS);
     CSEG_REQUIRE(plain && hs && ws && weights, "ms_fuse_argmax: null term arrays");
@@ -105,14 +108,38 @@ extern "C" int cseg_ms_fuse_argmax(int n_terms, const float* const* plain, const
         t.wt = weights[i];
     }
     const unsigned blocks = (unsigned)(((long)B * H * W + 255) / 256);
-#define LAUNCH(NT) hipLaunchKernelGGL((ms_fuse_kernel<NT, MsArgs>), dim3(blocks), dim3(256), 0, stream, A, pred, fused)
-    if (n_terms <= 1) LAUNCH(1);
-    else if (n_terms <= 2) LAUNCH(2);
-    else if (n_terms <= 4) LAUNCH(4);
-    else LAUNCH(8);
+#define LAUNCH(NT, ARGS) hipLaunchKernelGGL((ms_fuse_kernel<NT, decltype(ARGS)>), dim3(blocks), dim3(256), 0, stream, ARGS, pred, fused)
+#define LAUNCH_BY_TERMS(ARGS)           \
+    do {                                \
+        if (n_terms <= 1) LAUNCH(1, ARGS);      \
+        else if (n_terms <= 2) LAUNCH(2, ARGS); \
+        else if (n_terms <= 4) LAUNCH(4, ARGS); \
+        else LAUNCH(8, ARGS);           \
+    } while (0)
+    if (perm) {                          // everything is checked before the launch: a refused table launches nothing
+        int at = 0, val = 0;
+        const char* fault = ms_perm_fault(perm, K, &at, &val);
+        CSEG_REQUIRE(!fault, "ms_fuse_argmax: perm[%d] = %d %s (perm must be a permutation of the %d classes)", at, val, fault, K);
+        bool any_flipped = false;
+        for (int i = 0; i < n_terms; ++i) any_flipped = any_flipped || A.t[i].b;
+        CSEG_REQUIRE(any_flipped, "ms_fuse_argmax: a channel permutation was given but no term has a flipped map to apply it to");
+        MsPermuted<MsArgs> P;
+        static_cast<MsArgs&>(P) = A;
+        P.perm.fill(perm, K);
+        LAUNCH_BY_TERMS(P);
+    } else {
+        LAUNCH_BY_TERMS(A);
+    }
+#undef LAUNCH_BY_TERMS
 #undef LAUNCH
     CSEG_CHECK_LAUNCH("ms_fuse_kernel");
     return 1;
+}
+
+extern "C" int cseg_ms_fuse_argmax(int n_terms, const float* const* plain, const float* const* flipped, const int* hs,
+                                   const int* ws, const float* weights, int B, int K, int H, int W, uint8_t* pred,
+                                   float* fused, cseg_stream_t stream_) {
+    return cseg_ms_fuse_argmax_perm(n_terms, plain, flipped, hs, ws, weights, nullptr, B, K, H, W, pred, fused, stream_);
 }
 
 extern "C" int cseg_confusion_update(const uint8_t* pred, const int64_t* target, long N, int K, int ignore_index,

@@ -15,9 +15,11 @@
 // up to RG_IMAGES images is one launch, a larger one ceil(n / RG_IMAGES) launches on the same stream.
 #include "cseg_ms_fuse.h"
 
-extern "C" int cseg_ms_fuse_argmax_ragged(int n_images, int n_terms, const float* const* plain, const float* const* flipped,
-                                          const int* hs, const int* ws, const float* weights, const int* geometry, int K,
-                                          uint8_t* pred, float* fused, cseg_stream_t stream_) {
+// cseg_ms_fuse_argmax_ragged_perm: the flipped maps' classes permuted as in cseg_ms_fuse_argmax_perm (one table for the batch), the
+// MsPermuted<RgArgs> instances; a null table launches the instances the entry point without it always has.
+extern "C" int cseg_ms_fuse_argmax_ragged_perm(int n_images, int n_terms, const float* const* plain, const float* const* flipped,
+                                               const int* hs, const int* ws, const float* weights, const uint8_t* perm,
+                                               const int* geometry, int K, uint8_t* pred, float* fused, cseg_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     CSEG_REQUIRE(n_images >= 1 && n_images <= 65535, "ms_fuse_argmax_ragged: %d images (1 to 65535 are supported)", n_images);
     CSEG_REQUIRE(n_terms >= 1 && n_terms <= MS_MAX_TERMS, "ms_fuse_argmax_ragged: %d terms (1 to %d are supported)", n_terms,
@@ -44,9 +46,21 @@ extern "C" int cseg_ms_fuse_argmax_ragged(int n_images, int n_terms, const float
                          hs[e], ws[e]);
         }
     }
+    MsPermuted<RgArgs> P;
+    if (perm) {
+        int at = 0, val = 0;
+        const char* fault = ms_perm_fault(perm, K, &at, &val);
+        CSEG_REQUIRE(!fault, "ms_fuse_argmax_ragged: perm[%d] = %d %s (perm must be a permutation of the %d classes)", at, val, fault,
+                     K);
+        bool any_flipped = false;
+        for (int e = 0; flipped && e < n_images * n_terms; ++e) any_flipped = any_flipped || flipped[e];
+        CSEG_REQUIRE(any_flipped,
+                     "ms_fuse_argmax_ragged: a channel permutation was given but no term has a flipped map to apply it to");
+        P.perm.fill(perm, K);
+    }
     long pix0 = 0;
     for (int first = 0; first < n_images; first += RG_IMAGES) {
-        RgArgs A;
+        RgArgs& A = P;
         A.n_images = n_images - first < RG_IMAGES ? n_images - first : RG_IMAGES;
         A.n = n_terms;
         A.K = K;
@@ -74,13 +88,27 @@ extern "C" int cseg_ms_fuse_argmax_ragged(int n_images, int n_terms, const float
                 t.wt = weights[e];
             }
         }
-#define LAUNCH(NT) hipLaunchKernelGGL((ms_fuse_kernel<NT, RgArgs>), dim3((unsigned)blocks), dim3(256), 0, stream, A, pred, fused)
-        if (n_terms <= 1) LAUNCH(1);
-        else if (n_terms <= 2) LAUNCH(2);
-        else if (n_terms <= 4) LAUNCH(4);
-        else LAUNCH(8);
+#define LAUNCH(NT, ARGS) \
+    hipLaunchKernelGGL((ms_fuse_kernel<NT, std::decay<decltype(ARGS)>::type>), dim3((unsigned)blocks), dim3(256), 0, stream, ARGS, pred, fused)
+#define LAUNCH_BY_TERMS(ARGS)                   \
+    do {                                        \
+        if (n_terms <= 1) LAUNCH(1, ARGS);      \
+        else if (n_terms <= 2) LAUNCH(2, ARGS); \
+        else if (n_terms <= 4) LAUNCH(4, ARGS); \
+        else LAUNCH(8, ARGS);                   \
+    } while (0)
+        if (perm) LAUNCH_BY_TERMS(P);
+        else LAUNCH_BY_TERMS(A);
+#undef LAUNCH_BY_TERMS
 #undef LAUNCH
         CSEG_CHECK_LAUNCH("ms_fuse_kernel (ragged)");
     }
     return 1;
+}
+
+extern "C" int cseg_ms_fuse_argmax_ragged(int n_images, int n_terms, const float* const* plain, const float* const* flipped,
+                                          const int* hs, const int* ws, const float* weights, const int* geometry, int K,
+                                          uint8_t* pred, float* fused, cseg_stream_t stream_) {
+    return cseg_ms_fuse_argmax_ragged_perm(n_images, n_terms, plain, flipped, hs, ws, weights, nullptr, geometry, K, pred, fused,
+                                           stream_);
 }

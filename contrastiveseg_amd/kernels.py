@@ -1119,13 +1119,27 @@ def ohem_ce(seg, target, weight=None, ignore_index=-1, thresh=0.7, min_kept=1, s
 MS_MAX_TERMS = 8
 
 
+def _perm_table(perm, K, what):
+    """perm = None | a sequence or tensor of K ints -> the host byte table of the *_perm entry points. Length and byte range are
+    checked here; that it is a permutation of the K classes is the library's to check."""
+    vals = [int(v) for v in (perm.tolist() if torch.is_tensor(perm) else perm)]
+    if len(vals) != K:
+        raise RuntimeError("%s: perm has %d entries for %d classes" % (what, len(vals), K))
+    for k, v in enumerate(vals):
+        if v < 0 or v > 255:
+            raise RuntimeError("%s: perm[%d] = %d is not a class index (0 to %d)" % (what, k, v, K - 1))
+    return (ctypes.c_ubyte * K)(*vals)
+
+
 @torch.no_grad()
-def ms_fuse_argmax(terms, H, W, want_fused=False, want_pred=True):
+def ms_fuse_argmax(terms, H, W, want_fused=False, want_pred=True, perm=None):
     """segmentor/tester.py:310-327, 380-398 + the argmax of :189 without any [B,K,H,W] tensor. `terms` is a list of
     (plain, flipped or None, weight): plain = the net's coarse logits [B,K,h,w] at one scale, flipped = its output for the
     horizontally mirrored input. -> pred u8 [B,H,W] (first index among equal maxima), or (pred, fused) with
     fused = sum_i weight_i * (U(plain_i) + flip(U(flipped_i))) as fp32 [B,K,H,W] when want_fused (save_prob, tests);
-    pred is None when want_pred is False."""
+    pred is None when want_pred is False. perm (K ints, sequence or tensor): output class k reads class perm[k] of every flipped
+    map -- the left / right classes of a human-parsing set trade places under the mirror -- which equals the call on
+    flipped.index_select(1, perm), bit for bit, without the copy."""
     n = len(terms)
     if n < 1 or n > MS_MAX_TERMS:
         raise RuntimeError("ms_fuse_argmax: %d terms (1 to %d are supported)" % (n, MS_MAX_TERMS))
@@ -1149,8 +1163,12 @@ def ms_fuse_argmax(terms, H, W, want_fused=False, want_pred=True):
     dev = terms[0][0].device
     pred = torch.empty(B, int(H), int(W), dtype=U8, device=dev) if want_pred else None
     fused = torch.empty(B, K, int(H), int(W), dtype=F32, device=dev) if want_fused else None
-    _hip.call("cseg_ms_fuse_argmax", n, pa, pb, hs, ws, wt, B, K, int(H), int(W), _pf(pred) if want_pred else _null(),
-              _pf(fused) if want_fused else _null(), _hip.stream_ptr())
+    outs = (_pf(pred) if want_pred else _null(), _pf(fused) if want_fused else _null(), _hip.stream_ptr())
+    if perm is None:
+        _hip.call("cseg_ms_fuse_argmax", n, pa, pb, hs, ws, wt, B, K, int(H), int(W), *outs)
+    else:
+        _hip.call("cseg_ms_fuse_argmax_perm", n, pa, pb, hs, ws, wt, _perm_table(perm, K, "ms_fuse_argmax"), B, K, int(H), int(W),
+                  *outs)
     return (pred, fused) if want_fused else pred
 
 
@@ -1158,14 +1176,14 @@ RaggedScores = collections.namedtuple("RaggedScores", ["pred", "preds", "fused",
 
 
 @torch.no_grad()
-def ms_fuse_argmax_ragged(images, want_fused=False, want_pred=True):
+def ms_fuse_argmax_ragged(images, want_fused=False, want_pred=True, perm=None):
     """ms_fuse_argmax for a batch of images of differing sizes, the list branches of segmentor/tester.py:328-341, 400-421 with the crop
     and argmax of :169-189 (csrc/ms_eval_ragged.hip). `images` is a list of (terms, (Hp, Wp), (h, w)): terms as in ms_fuse_argmax with
     maps [1,K,hc,wc], (Hp, Wp) the padded size whose geometry the upsampling and the mirror take, (h, w) the border, the unpadded
     top-left region, which alone is computed. Every image has the same K and the same number of terms.
     -> RaggedScores(pred, preds, fused, fuseds): pred the packed u8 buffer [sum h*w] (the images one after the other, each row-major)
     and preds its per-image [h,w] views; fused the packed fp32 buffer [K * sum h*w] (image-major, then [K,h,w]) and fuseds its
-    per-image [K,h,w] views. A pair that was not asked for is (None, None)."""
+    per-image [K,h,w] views. A pair that was not asked for is (None, None). perm: as in ms_fuse_argmax, one table for the batch."""
     n_img = len(images)
     if n_img < 1:
         raise RuntimeError("ms_fuse_argmax_ragged: images is empty")
@@ -1203,8 +1221,12 @@ def ms_fuse_argmax_ragged(images, want_fused=False, want_pred=True):
     # (an empty geometry is the library's to refuse: it gets real pointers to say so)
     pred = torch.empty(max(total, 1), dtype=U8, device=dev)[:total] if want_pred else None
     fused = torch.empty(max(K * total, 1), dtype=F32, device=dev)[:K * total] if want_fused else None
-    _hip.call("cseg_ms_fuse_argmax_ragged", n_img, n, pa, pb, hs, ws, wt, geo, K, _pf(pred) if want_pred else _null(),
-              _pf(fused) if want_fused else _null(), _hip.stream_ptr())
+    outs = (_pf(pred) if want_pred else _null(), _pf(fused) if want_fused else _null(), _hip.stream_ptr())
+    if perm is None:
+        _hip.call("cseg_ms_fuse_argmax_ragged", n_img, n, pa, pb, hs, ws, wt, geo, K, *outs)
+    else:
+        _hip.call("cseg_ms_fuse_argmax_ragged_perm", n_img, n, pa, pb, hs, ws, wt, _perm_table(perm, K, "ms_fuse_argmax_ragged"), geo,
+                  K, *outs)
     preds, fuseds, off = [], [], 0
     for h, w in sizes:
         if want_pred:
@@ -3524,10 +3546,17 @@ def bn_bwd(dy, x, out, mean_invstd, weight, bias, mode, training, want_dx, amax=
 AUG_PARAM_INTS = 12
 
 
+def _lut_mirrored(lut_mirrored, what):
+    if lut_mirrored is not None and lut_mirrored.numel() != 256:
+        raise RuntimeError("%s: lut_mirrored has %d entries, expected 256" % (what, lut_mirrored.numel()))
+    return _opt(lut_mirrored, I16, "lut_mirrored")
+
+
 @torch.no_grad()
-def augment_batch(img_u8, lab_u8, lut, params, out_hw, div_value, mean, std):
+def augment_batch(img_u8, lab_u8, lut, params, out_hw, div_value, mean, std, lut_mirrored=None):
     """img_u8 [B,Hs,Ws,3] u8, lab_u8 [B,Hs,Ws] u8 or None, lut i16 [256] or None, params i32 [B,AUG_PARAM_INTS]
-    (host tensor is uploaded) -> (img f32 [B,3,Ht,Wt], labelmap i64 [B,Ht,Wt] or None)."""
+    (host tensor is uploaded) -> (img f32 [B,3,Ht,Wt], labelmap i64 [B,Ht,Wt] or None). lut_mirrored i16 [256] (lut o swap of
+    random_hflip.swap_pair): the table of the flipped samples; None = no swap."""
     B, Hs, Ws, _ = img_u8.shape
     Ht, Wt = out_hw
     dev = img_u8.device
@@ -3537,9 +3566,13 @@ def augment_batch(img_u8, lab_u8, lut, params, out_hw, div_value, mean, std):
     mean3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
     std3 = (ctypes.c_float * 3)(*[float(v) for v in std])
     U8 = torch.uint8
-    _hip.call("cseg_augment_batch", _p(img_u8, U8, "img"), _opt(lab_u8, U8, "labelmap"), _opt(lut, I16, "lut"),
-              _p(params, I32, "params"), B, Hs, Ws, Ht, Wt, float(div_value), mean3, std3, _p(out, F32, "out_img"),
-              _opt(out_lab, I64, "out_lab"), _hip.stream_ptr())
+    tail = (_p(params, I32, "params"), B, Hs, Ws, Ht, Wt, float(div_value), mean3, std3, _p(out, F32, "out_img"),
+            _opt(out_lab, I64, "out_lab"), _hip.stream_ptr())
+    if lut_mirrored is None:
+        _hip.call("cseg_augment_batch", _p(img_u8, U8, "img"), _opt(lab_u8, U8, "labelmap"), _opt(lut, I16, "lut"), *tail)
+    else:
+        _hip.call("cseg_augment_batch_swap", _p(img_u8, U8, "img"), _opt(lab_u8, U8, "labelmap"), _opt(lut, I16, "lut"),
+                  _lut_mirrored(lut_mirrored, "augment_batch"), *tail)
     return out, out_lab
 
 
@@ -3589,9 +3622,10 @@ def resize_ragged(img_u8, lab_u8, params, offsets):
 
 
 @torch.no_grad()
-def augment_ragged(img_u8, lab_u8, lut, params, offsets, out_hw, div_value, mean, std, mid=None):
+def augment_ragged(img_u8, lab_u8, lut, params, offsets, out_hw, div_value, mean, std, mid=None, lut_mirrored=None):
     """Stage 2. Arguments as resize_ragged, `mid` = its result (needed when a record has W1 > 0), lut i16 [256] or None
-    -> (img f32 [B,3,Ht,Wt], labelmap i64 [B,Ht,Wt] or None)."""
+    -> (img f32 [B,3,Ht,Wt], labelmap i64 [B,Ht,Wt] or None). lut_mirrored i16 [256] (lut o swap of random_hflip.swap_pair): the
+    table of the samples with an odd number of flips (record ints 4 ^ 7 ^ 12); None = no swap."""
     dev = img_u8.device
     U8 = torch.uint8
     Ht, Wt = out_hw
@@ -3604,8 +3638,12 @@ def augment_ragged(img_u8, lab_u8, lut, params, offsets, out_hw, div_value, mean
     out_lab = torch.empty(B, Ht, Wt, dtype=I64, device=dev) if lab_u8 is not None else None
     mean3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
     std3 = (ctypes.c_float * 3)(*[float(v) for v in std])
-    _hip.call("cseg_augment_ragged", _p(img_u8, U8, "img"), _opt(lab_u8, U8, "labelmap"), n, _opt(mid_img, U8, "mid_img"),
-              _opt(mid_lab, U8, "mid_lab"), m, _opt(lut, I16, "lut"), _p(pd, I32, "params"), _p(od, I64, "offsets"),
-              ctypes.c_void_p(ph.data_ptr()), ctypes.c_void_p(oh.data_ptr()), B, Ht, Wt, float(div_value), mean3, std3,
-              _p(out, F32, "out_img"), _opt(out_lab, I64, "out_lab"), _hip.stream_ptr())
+    head = (_p(img_u8, U8, "img"), _opt(lab_u8, U8, "labelmap"), n, _opt(mid_img, U8, "mid_img"), _opt(mid_lab, U8, "mid_lab"), m,
+            _opt(lut, I16, "lut"))
+    tail = (_p(pd, I32, "params"), _p(od, I64, "offsets"), ctypes.c_void_p(ph.data_ptr()), ctypes.c_void_p(oh.data_ptr()), B, Ht, Wt,
+            float(div_value), mean3, std3, _p(out, F32, "out_img"), _opt(out_lab, I64, "out_lab"), _hip.stream_ptr())
+    if lut_mirrored is None:
+        _hip.call("cseg_augment_ragged", *head, *tail)
+    else:
+        _hip.call("cseg_augment_ragged_swap", *head, _lut_mirrored(lut_mirrored, "augment_ragged"), *tail)
     return out, out_lab

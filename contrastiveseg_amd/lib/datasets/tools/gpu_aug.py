@@ -26,7 +26,13 @@ Composition rule (GPUAugCompose.draw). The sequence is walked in order with a PE
 resampling consumes it as that stage's `mirror` flag (cv2.resize of the flipped image is not the flip of cv2.resize: cv2's
 nearest rule min(floor(d * scale), W - 1) and the cubic taps are not symmetric on the pixel grid); a crop under a pending mirror
 takes the mirrored window x -> W - x - tw and leaves the bit pending; what is pending at the end is the output flip. A
-resampling to the size the image already has is a copy (cv::resize does that) and counts as no resampling."""
+resampling to the size the image already has is a copy (cv::resize does that) and counts as no resampling.
+
+random_hflip.swap_pair (the LIP configs: left / right arm, leg, shoe). An applied flip also trades the listed label ids (swap_table).
+That is a value map, which draws no random number and commutes with the nearest resamplings, the crop and the padding, so a sample's
+labels are swapped iff its number of applied flips is odd: stage-1 mirror ^ stage-2 mirror ^ output flip on the ragged path, the flip
+bit on the one-kernel path (a mirrored crop window leaves its flip pending and does not count). The kernels pick between two
+tables, lut and lut_mirrored = lut o swap."""
 import math
 import random
 
@@ -37,6 +43,30 @@ from contrastiveseg_amd import kernels as K
 
 SUPPORTED = ('random_resize', 'random_crop', 'random_hflip', 'random_brightness', 'resize')
 RESAMPLINGS = ('resize', 'random_resize')
+
+
+def swap_table(swap_pair):
+    """random_hflip.swap_pair -> the value map of RandomHFlip._process_labelmap (cv2_aug_transforms.py:151-162) as uint8 [256], or
+    None without pairs. The reference assigns, for every pair in order and from a copy of the flipped map, labelmap[temp == a] = b and
+    labelmap[temp == b] = a: swap[v] is the partner of v in the LAST pair that mentions v, v itself where none does. It acts on raw
+    label ids, ahead of the label_list / reduce_zero_label encoding. 255 is the pad / ignore value of the label path (a label-free
+    sample reads 255, ReLabel maps it to -1) and cannot be swapped."""
+    if not swap_pair:
+        return None
+    if not isinstance(swap_pair, (list, tuple)):
+        raise ValueError('random_hflip.swap_pair {!r}: expected a list of [a, b] pairs'.format(swap_pair))
+    swap = np.arange(256, dtype=np.uint8)
+    for pair in swap_pair:
+        if not isinstance(pair, (list, tuple)) or len(pair) != 2 or \
+                not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in pair):
+            raise ValueError('random_hflip.swap_pair entry {!r}: expected two integer label ids [a, b]'.format(pair))
+        a, b = int(pair[0]), int(pair[1])
+        if a == 255 or b == 255:
+            raise ValueError('random_hflip.swap_pair entry {!r} mentions 255, the pad / ignore value of the label path'.format(pair))
+        if not (0 <= a <= 254 and 0 <= b <= 254):
+            raise ValueError('random_hflip.swap_pair entry {!r}: label ids must lie in 0..254'.format(pair))
+        swap[a], swap[b] = b, a
+    return swap
 
 
 class SampleParams(object):
@@ -93,8 +123,12 @@ class GPUAugCompose(object):
         if 'random_crop' in self.seq and rc.get('method', 'random') not in ('random', 'center'):
             raise NotImplementedError("random_crop.method {!r}: only 'random' / 'center'".format(rc.get('method')))
         hf = self.cfg.get('random_hflip', {})
-        if 'random_hflip' in self.seq and hf.get('swap_pair'):
-            raise NotImplementedError('random_hflip.swap_pair (left/right label swap) is not implemented')
+        self.swap = swap_table(hf.get('swap_pair')) if 'random_hflip' in self.seq else None
+        if self.swap is not None and self.seq.count('random_hflip') > 1 and not np.array_equal(self.swap[self.swap], np.arange(256)):
+            # the kernels swap by the PARITY of the applied flips, which is the reference's result only when swapping twice is the
+            # identity; pairs that share an id are not, and two flips would apply such a map twice
+            raise NotImplementedError('random_hflip.swap_pair {!r} with pairs that share an id, in a trans_seq with more than one '
+                                      'random_hflip, is outside the accelerated data path'.format(hf.get('swap_pair')))
         if 'resize' in self.seq:
             rz = self.cfg.get('resize', {})
             if not any(rz.get(k) is not None for k in ('target_size', 'min_side_length', 'max_side_length')):
@@ -229,6 +263,12 @@ class GPUBatchTransform(object):
             lut = np.arange(256, dtype=np.int16) - 1              # default_loader.py:83-92 (uint8 wrap: 0 -> 255)
             lut[0] = 255
             self.lut = torch.from_numpy(lut)
+        # random_hflip.swap_pair: the table of the samples with an odd number of applied flips, lut o swap (the swap acts on raw
+        # ids, the encoding follows); over the identity table when there is no encoding
+        self.lut_mirrored = None
+        if self.aug.swap is not None:
+            base = self.lut.numpy() if self.lut is not None else np.arange(256, dtype=np.int16)
+            self.lut_mirrored = torch.from_numpy(np.ascontiguousarray(base[self.aug.swap].astype(np.int16)))
 
     def _target(self, samples):
         """(Wt, Ht) of the batch: the fixed input size, or under diverse_size the single sample's own size, padded right / down to
@@ -288,12 +328,15 @@ class GPUBatchTransform(object):
         on the device. -> img, labelmap, aug_params (the records of the path taken), border_size [(tw, th)], pad_offset [(left, up)]."""
         if self.lut is not None and self.lut.device != img_u8.device:
             self.lut = self.lut.to(img_u8.device)
+        if self.lut_mirrored is not None and self.lut_mirrored.device != img_u8.device:
+            self.lut_mirrored = self.lut_mirrored.to(img_u8.device)
         lab_u8 = None if lab_u8 is None else lab_u8.contiguous()
+        swap = {} if self.lut_mirrored is None else {'lut_mirrored': self.lut_mirrored}      # without pairs: the calls as they were
         if sizes is None and self.aug.canonical and self.size_mode == 'fix_size':
             B, Hs, Ws, _ = img_u8.shape
             params = self.plan([(Ws, Hs)] * B)
             img, lab = K.augment_batch(img_u8.contiguous(), lab_u8, self.lut, params, (self.target_h, self.target_w), self.div,
-                                       self.mean, self.std)
+                                       self.mean, self.std, **swap)
             rows = params.tolist()
             return {'img': img, 'labelmap': lab, 'aug_params': params, 'border_size': [(r[4], r[5]) for r in rows],
                     'pad_offset': [(r[8], r[9]) for r in rows]}
@@ -303,7 +346,7 @@ class GPUBatchTransform(object):
         params, offsets, (Wt, Ht) = self.plan_ragged(sizes)
         img_u8 = img_u8.contiguous()
         mid = K.resize_ragged(img_u8, lab_u8, params, offsets) if bool((params[:, 2] > 0).any()) else None
-        img, lab = K.augment_ragged(img_u8, lab_u8, self.lut, params, offsets, (Ht, Wt), self.div, self.mean, self.std, mid=mid)
+        img, lab = K.augment_ragged(img_u8, lab_u8, self.lut, params, offsets, (Ht, Wt), self.div, self.mean, self.std, mid=mid, **swap)
         rows = params.tolist()
         return {'img': img, 'labelmap': lab, 'aug_params': params, 'aug_offsets': offsets,
                 'border_size': [(r[10], r[11]) for r in rows], 'pad_offset': [(r[14], r[15]) for r in rows]}

@@ -22,6 +22,10 @@ region into packed buffers, which the confusion matrix takes as they are. The re
 scaling align methods), so under only_pad its final cv2.resize(outputs[:border_h, :border_w], ori_img_size, INTER_CUBIC) (:180-181)
 has equal source and target size and copies.
 
+test.flip_swap_pair (this project's own key, like contrast.use_ohem; absent by default, which is the reference's behaviour): a list of
+class pairs that trade places under the mirror (LIP: left / right arm, leg, shoe). The mirrored pass of ms_test is then read through
+that channel permutation inside the scoring kernel (kernels.ms_fuse_argmax(perm=...)); the sliding-crop modes refuse the key.
+
 Outside the accelerated path, refused by name: ms_test_depth, crf_ss_test, the offset path; align_method scale_and_pad / only_scale
 (border_size is scaled there and the final cubic resize is a real one) and size_mode max_size / multi_size; under diverse_size a
 pad_mode other than an explicit pad_right_down (the reference's crop at :180 is top-left, so only right / down padding makes its
@@ -80,7 +84,36 @@ def check_config(configer):
                 raise NotImplementedError("test.data_transformer {}: size_mode diverse_size needs pad_mode 'pad_right_down' stated "
                                           'explicitly: the prediction of a padded image is cropped top-left, so only right / down '
                                           "padding makes it the image's prediction, and an absent pad_mode means 'random'".format(dt))
+    flip_swap_perm(configer, mode)
     return mode, scales, weights
+
+
+def flip_swap_perm(configer, mode=None):
+    """test.flip_swap_pair -- this project's own key, the reference has none: its tester mirrors without swapping channels
+    (:345-349, :380-421), also for LIP, and that stays the default -- a list of [a, b] class pairs that trade places under the
+    mirror. -> the channel permutation ms_test hands to kernels.ms_fuse_argmax / ms_fuse_argmax_ragged (output class k reads class
+    perm[k] of the mirrored pass), or None without the key. Pairs that share a class do not describe an exchange of channels and
+    are refused."""
+    pairs = configer.get('test', 'flip_swap_pair') if configer.exists('test', 'flip_swap_pair') else None
+    if not pairs:
+        return None
+    if mode is None:
+        mode = configer.get('test', 'mode') if configer.exists('test', 'mode') else 'ss_test'
+    if mode in CROP_MODES:
+        raise NotImplementedError('test.flip_swap_pair together with test.mode {!r}: the sliding-crop kernel takes no channel '
+                                  'permutation; use ss_test / ms_test'.format(mode))
+    n = configer.get('data', 'num_classes')
+    perm = list(range(n))
+    for pair in pairs:
+        if not isinstance(pair, (list, tuple)) or len(pair) != 2 or not all(isinstance(v, int) and not isinstance(v, bool) for v in pair):
+            raise ValueError('test.flip_swap_pair entry {!r}: expected two class indices [a, b]'.format(pair))
+        if not all(0 <= v < n for v in pair):
+            raise ValueError('test.flip_swap_pair entry {!r} lies outside the {} classes of data.num_classes'.format(pair, n))
+        perm[pair[0]], perm[pair[1]] = pair[1], pair[0]
+    if sorted(perm) != list(range(n)):
+        raise ValueError('test.flip_swap_pair {!r} is not a permutation of the classes: a class is mentioned by more than one pair'
+                         .format(pairs))
+    return perm
 
 
 def is_ragged(configer):
@@ -145,6 +178,7 @@ class Tester(object):
         self.configer = configer
         self.mode, self.scales, self.weights = check_config(configer)
         self.crop_size = resolve_crop_size(configer, self.mode)
+        self.perm = flip_swap_perm(configer, self.mode)
         if self.mode == 'mscrop_test' and configer.exists('test', 'scale_weights') and configer.get('test', 'scale_weights') is not None:
             Log.warn('test.scale_weights is ignored in mscrop_test, as in the reference')
         from contrastiveseg_amd.lib.models.model_manager import ModelManager
@@ -184,7 +218,8 @@ class Tester(object):
     @torch.no_grad()
     def _fuse(self, terms, inputs, want_fused):
         h, w = inputs.shape[-2:]
-        return K.ms_fuse_argmax(terms, h, w, want_fused=want_fused)
+        mirrored = any(b is not None for _, b, _ in terms)          # test.flip_swap_pair acts on the mirrored pass only
+        return K.ms_fuse_argmax(terms, h, w, want_fused=want_fused, perm=self.perm if mirrored else None)
 
     @torch.no_grad()
     def _fuse_ragged(self, inputs, scales, weights, flip, borders, want_fused):
@@ -205,7 +240,7 @@ class Tester(object):
                 terms.append((a, b, 1.0 if weights is None else weights[i]))
             padded = tuple(x.shape[-2:])
             images.append((terms, padded, padded if borders is None else (int(borders[k][0]), int(borders[k][1]))))
-        return K.ms_fuse_argmax_ragged(images, want_fused=want_fused)
+        return K.ms_fuse_argmax_ragged(images, want_fused=want_fused, perm=self.perm if flip else None)
 
     @torch.no_grad()
     def ss_test(self, inputs, scale=1, want_fused=False, borders=None):

@@ -13,12 +13,16 @@ class DataHelper(object):
         self.trainer = trainer
 
     def prepare_data(self, data_dict, want_reverse=False):
+        """-> ((inputs, targets), batch_size); with want_reverse (the LIP validation pass, reference :69-91, :137-148) ->
+        ((inputs, targets, inputs_rev, targets_rev), batch_size), the reversed tensors being torch.flip along the last axis."""
         img = data_dict['img']
         target = data_dict['labelmap']
         dev = self.trainer.module_runner.device()
         if img.device != dev:
             img = img.to(dev, non_blocking=True)
             target = target.to(dev, non_blocking=True)
+        if want_reverse:
+            return ([img], target, [torch.flip(img, [img.dim() - 1])], torch.flip(target, [target.dim() - 1])), img.shape[0]
         return ([img], target), img.shape[0]
 
 

@@ -75,6 +75,55 @@ def plan_enqueue(counts, seg_ptr, pix_ptr, memory_size, pixel_update_freq):
     return seg_jobs, pix_rows, seg_ptr, pix_ptr
 
 
+LIP_SWAP_PAIRS = ((14, 15), (16, 17), (18, 19))        # left / right arm, leg, shoe: reference :337-343, hard-coded there
+
+
+def lip_mirror_perm(n_channels):
+    """The channel permutation of the mirrored half in the LIP validation pass, or None: the reference swaps its three pairs iff
+    the map has 20 channels (:337) and averages image and mirror without a swap at any other class count."""
+    if n_channels != 20:
+        return None
+    perm = list(range(n_channels))
+    for a, b in LIP_SWAP_PAIRS:
+        perm[a], perm[b] = b, a
+    return perm
+
+
+@torch.no_grad()
+def score_mirrored_pair(seg, targets, hist=None, score=None):
+    """One batch of the LIP validation pass (reference :335-346). seg [2B,K,h,w]: the net's output for cat([x, flip(x)]), whose second
+    half is the mirrored operand; targets [B,H,W]. The prediction is the argmax of the upsampled average of the first half and the
+    un-mirrored second half, whose left / right channels are swapped (lip_mirror_perm).
+    hist (i64 [K,K] on the device): the fused path -- the two halves, contiguous views, go to kernels.ms_fuse_argmax as one term of
+    weight 0.5 with the permutation, then kernels.confusion_update; no [B,K,H,W] tensor exists.
+    score (RunningScore): the reference's tensor ops literally, then the interpolate + argmax + update of the default pass."""
+    if (hist is None) == (score is None):
+        raise ValueError('score_mirrored_pair takes either hist (fused path) or score (torch composition)')
+    if seg.dim() != 4 or seg.shape[0] % 2 or seg.shape[0] // 2 != targets.shape[0]:
+        raise ValueError('score_mirrored_pair: seg {} is not the output for an image batch and its mirror with targets {}'
+                         .format(tuple(seg.shape), tuple(targets.shape)))
+    half = seg.shape[0] // 2
+    if hist is not None:
+        pred = K.ms_fuse_argmax([(seg[:half], seg[half:], 0.5)], targets.shape[-2], targets.shape[-1],
+                                perm=lip_mirror_perm(seg.shape[1]))
+        return K.confusion_update(pred, targets, hist, ignore_index=-1)
+    outputs_ = seg
+    outputs = outputs_[0:half, :, :, :].clone()
+    outputs_rev = outputs_[half:2 * half, :, :, :].clone()
+    if outputs_rev.shape[1] == 20:
+        outputs_rev[:, 14, :, :] = outputs_[half:2 * half, 15, :, :]
+        outputs_rev[:, 15, :, :] = outputs_[half:2 * half, 14, :, :]
+        outputs_rev[:, 16, :, :] = outputs_[half:2 * half, 17, :, :]
+        outputs_rev[:, 17, :, :] = outputs_[half:2 * half, 16, :, :]
+        outputs_rev[:, 18, :, :] = outputs_[half:2 * half, 19, :, :]
+        outputs_rev[:, 19, :, :] = outputs_[half:2 * half, 18, :, :]
+    outputs_rev = torch.flip(outputs_rev, [3])
+    outputs = (outputs + outputs_rev) / 2.
+    up = nn.functional.interpolate(outputs, size=targets.shape[-2:], mode='bilinear', align_corners=True)
+    score.update(up.argmax(1), targets)
+    return score
+
+
 class Trainer(object):
     def __init__(self, configer, train_loader=None, val_loader=None):
         self.configer = configer
@@ -396,7 +445,23 @@ class Trainer(object):
         # second one (csrc/ms_eval.hip) -- the label-resolution logits (319 MB per batch of 8 at 19 classes) never exist
         fused = os.environ.get('CSEG_VAL_FUSED', '0') == '1'
         hist = None
+        # dataset 'lip' (reference :320-346): one forward on the batch and its mirror together, the left / right channels of the
+        # mirrored half swapped, the score from the average; no validation loss in this branch, as in the reference. Fused by
+        # default (the branch has no earlier behaviour to keep); CSEG_VAL_FUSED=0, set explicitly, is the torch composition.
+        lip = self.configer.exists('dataset') and self.configer.get('dataset') == 'lip'
+        lip_fused = os.environ.get('CSEG_VAL_FUSED', '1') != '0'
         for data_dict in (self.val_loader if data_loader is None else data_loader):
+            if lip:
+                (inputs, targets, inputs_rev, _), batch_size = self.data_helper.prepare_data(data_dict, want_reverse=True)
+                outputs = self.seg_net(torch.cat([inputs[0], inputs_rev[0]], dim=0), is_eval=True)
+                seg = outputs['seg'] if isinstance(outputs, dict) else outputs
+                if lip_fused:
+                    if hist is None:
+                        hist = torch.zeros(score.n_classes, score.n_classes, dtype=torch.int64, device=targets.device)
+                    score_mirrored_pair(seg, targets, hist=hist)
+                else:
+                    score_mirrored_pair(seg, targets, score=score)
+                continue
             (inputs, targets), batch_size = self.data_helper.prepare_data(data_dict)
             outputs = self.seg_net(*inputs, is_eval=True)
             self.val_losses.update(self.pixel_loss(outputs, targets).item(), batch_size)

@@ -733,6 +733,12 @@ int cseg_ocr_attn_bwd(const float* q, const float* key, const float* value, cons
 int cseg_augment_batch(const uint8_t* img, const uint8_t* lab, const int16_t* lut, const int32_t* params, int B, int Hs,
                        int Ws, int Ht, int Wt, float div_value, const float* mean3, const float* std3, float* out_img,
                        int64_t* out_lab, cseg_stream_t stream);
+/* The same with RandomHFlip's swap_pair (cv2_aug_transforms.py:151-162: a flipped label map trades its left / right ids):
+ * lut_mirrored [256] i16 = lut o swap is the table of the samples with flip = 1, lut (or the raw id when lut is NULL) that of the
+ * others. lut_mirrored NULL = no swap, which is what cseg_augment_batch calls this with. The image output does not depend on it. */
+int cseg_augment_batch_swap(const uint8_t* img, const uint8_t* lab, const int16_t* lut, const int16_t* lut_mirrored,
+                            const int32_t* params, int B, int Hs, int Ws, int Ht, int Wt, float div_value, const float* mean3,
+                            const float* std3, float* out_img, int64_t* out_lab, cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GPU data pipeline for mixed-size datasets (csrc/augment_ragged.hip): the chain above for a RAGGED batch -- B images of
@@ -772,6 +778,15 @@ int cseg_augment_ragged(const uint8_t* img, const uint8_t* lab, long src_pixels,
                         long mid_pixels, const int16_t* lut, const int32_t* params, const int64_t* offsets,
                         const int32_t* params_host, const int64_t* offsets_host, int B, int Ht, int Wt, float div_value,
                         const float* mean3, const float* std3, float* out_img, int64_t* out_lab, cseg_stream_t stream);
+/* Stage 2 with RandomHFlip's swap_pair: lut_mirrored [256] i16 = lut o swap is the table of the samples that went through an ODD
+ * number of flips, mirror1 ^ mirror2 ^ flip (ints 4, 7, 12; a value map commutes with the nearest resamplings, the crop and the
+ * padding, and two flips swap twice), lut (or the raw id) that of the others. NULL = no swap, which is what cseg_augment_ragged
+ * calls this with. Stage 1 keeps raw ids and has no such table. The image output does not depend on it. */
+int cseg_augment_ragged_swap(const uint8_t* img, const uint8_t* lab, long src_pixels, const uint8_t* mid_img, const uint8_t* mid_lab,
+                             long mid_pixels, const int16_t* lut, const int16_t* lut_mirrored, const int32_t* params,
+                             const int64_t* offsets, const int32_t* params_host, const int64_t* offsets_host, int B, int Ht, int Wt,
+                             float div_value, const float* mean3, const float* std3, float* out_img, int64_t* out_lab,
+                             cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Test phase (csrc/ms_eval.hip).  Replaces the tensor work of segmentor/tester.py:310-327, 380-398 (ss_test / ms_test) with
@@ -793,6 +808,15 @@ int cseg_augment_ragged(const uint8_t* img, const uint8_t* lab, long src_pixels,
  * ------------------------------------------------------------------------------------------------ */
 int cseg_ms_fuse_argmax(int n_terms, const float* const* plain, const float* const* flipped, const int* hs, const int* ws,
                         const float* weights, int B, int K, int H, int W, uint8_t* pred, float* fused, cseg_stream_t stream);
+/* The fusion with a channel permutation on the mirrored operand (classes that trade places under a mirror: left / right arm, leg,
+ * shoe of a human-parsing set). perm: HOST array of K entries, copied into the argument block, or NULL for the identity (then this
+ * is cseg_ms_fuse_argmax). Output class k reads class perm[k] of every flipped map:
+ *   v = v + weights[i] * (U(plain[i])[k][y,x] + U(flipped[i])[perm[k]][y,W-1-x])
+ * which is the plain call on flipped maps gathered by perm along the class axis, bit for bit. Refused, with nothing launched: an
+ * entry >= K, a repeated entry (not a permutation), a non-NULL perm when no term has a flipped map. */
+int cseg_ms_fuse_argmax_perm(int n_terms, const float* const* plain, const float* const* flipped, const int* hs, const int* ws,
+                             const float* weights, const uint8_t* perm, int B, int K, int H, int W, uint8_t* pred, float* fused,
+                             cseg_stream_t stream);
 int cseg_confusion_update(const uint8_t* pred, const int64_t* target, long N, int K, int ignore_index, int64_t* confusion,
                           cseg_stream_t stream);
 
@@ -816,6 +840,11 @@ int cseg_confusion_update(const uint8_t* pred, const int64_t* target, long N, in
 int cseg_ms_fuse_argmax_ragged(int n_images, int n_terms, const float* const* plain, const float* const* flipped, const int* hs,
                                const int* ws, const float* weights, const int* geometry, int K, uint8_t* pred, float* fused,
                                cseg_stream_t stream);
+/* The ragged fusion with the channel permutation of cseg_ms_fuse_argmax_perm on every flipped map (one HOST table of K entries for
+ * the batch, or NULL for the identity); image b carries the bits cseg_ms_fuse_argmax_perm writes for it alone. The same refusals. */
+int cseg_ms_fuse_argmax_ragged_perm(int n_images, int n_terms, const float* const* plain, const float* const* flipped, const int* hs,
+                                    const int* ws, const float* weights, const uint8_t* perm, const int* geometry, int K,
+                                    uint8_t* pred, float* fused, cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Test phase, sliding crops (csrc/crop_eval.hip).  Replaces the tensor work of segmentor/tester.py:351-378, 505-523 (sscrop_test /
