@@ -148,17 +148,36 @@ static inline void launch_band(const float* d_out, int Ctot, int coff, int Cm, i
                        hs, ws, h0, w0, nY_max, BL_TY, act, dx);
 }
 
+// The route of one adjoint, decided in one place: the launcher below and cseg_bilinear_adjoint_plan (upcat.hip) both ask here.
+// route = 0 for the gather kernel, otherwise the tap count of the band instance (8, 12, 24 or BL_MAX_TAPS). taps, nY_max and lds
+// are what a band would need, whether or not one is taken.
+struct BilinearAdjointPlan {
+    int route, taps, nY_max;
+    size_t lds;
+};
+
+static inline BilinearAdjointPlan bilinear_adjoint_plan(int hs, int ws, int h0, int w0) {
+    const float sy = ac_scale(hs, h0), sx = ac_scale(ws, w0);
+    BilinearAdjointPlan p;
+    p.taps = sx > 0.f ? (int)(2.0f / sx) + 3 : w0;
+    p.nY_max = sy > 0.f ? (int)((float)(BL_TY + 1) / sy) + 3 : h0;
+    p.lds = sizeof(float) * ((size_t)p.nY_max * w0 + (size_t)p.nY_max * ws);
+    p.route = 0;
+    if (ws <= 256 && p.taps <= BL_MAX_TAPS && p.lds <= 64 * 1024)
+        p.route = p.taps <= 8 ? 8 : p.taps <= 12 ? 12 : p.taps <= 24 ? 24 : BL_MAX_TAPS;
+    return p;
+}
+
 template <bool MASKED>
 static inline int launch_bilinear_adjoint(const float* d_out, int Ctot, int coff, int Cm, int hs, int ws, int h0, int w0,
                                           int B, const float* act, float* dx, hipStream_t stream) {
-    const float sy = ac_scale(hs, h0), sx = ac_scale(ws, w0);
-    const int taps = sx > 0.f ? (int)(2.0f / sx) + 3 : w0;
-    const int nY_max = sy > 0.f ? (int)((float)(BL_TY + 1) / sy) + 3 : h0;
-    const size_t lds = sizeof(float) * ((size_t)nY_max * w0 + (size_t)nY_max * ws);
-    if (ws <= 256 && taps <= BL_MAX_TAPS && lds <= 64 * 1024) {
-        if (taps <= 8) launch_band<MASKED, 8>(d_out, Ctot, coff, Cm, hs, ws, h0, w0, B, nY_max, lds, act, dx, stream);
-        else if (taps <= 12) launch_band<MASKED, 12>(d_out, Ctot, coff, Cm, hs, ws, h0, w0, B, nY_max, lds, act, dx, stream);
-        else if (taps <= 24) launch_band<MASKED, 24>(d_out, Ctot, coff, Cm, hs, ws, h0, w0, B, nY_max, lds, act, dx, stream);
+    const BilinearAdjointPlan p = bilinear_adjoint_plan(hs, ws, h0, w0);
+    const int nY_max = p.nY_max;
+    const size_t lds = p.lds;
+    if (p.route) {
+        if (p.route == 8) launch_band<MASKED, 8>(d_out, Ctot, coff, Cm, hs, ws, h0, w0, B, nY_max, lds, act, dx, stream);
+        else if (p.route == 12) launch_band<MASKED, 12>(d_out, Ctot, coff, Cm, hs, ws, h0, w0, B, nY_max, lds, act, dx, stream);
+        else if (p.route == 24) launch_band<MASKED, 24>(d_out, Ctot, coff, Cm, hs, ws, h0, w0, B, nY_max, lds, act, dx, stream);
         else launch_band<MASKED, BL_MAX_TAPS>(d_out, Ctot, coff, Cm, hs, ws, h0, w0, B, nY_max, lds, act, dx, stream);
     } else {
         dim3 grid((hs * ws + 255) / 256, Cm, B);

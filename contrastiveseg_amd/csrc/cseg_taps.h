@@ -1,7 +1,12 @@
 // The index arithmetic of bilinear(align_corners=True) upsampling, shared by everything that works on an upsampled map without building
 // it: the segmentation terms (upsample_ce / ohem / lovasz / rmi), the test-phase fusions (ms_eval / crop_eval) and the adjoint of the
-// exchange units (cseg_bilinear.h). torch's own fp32 index arithmetic, so taps and weights are torch's. DESIGN.md section 26 says what
-// lives here and what must not: indices, adjoint weights, loop nests -- never the value blends.
+// exchange units (cseg_bilinear.h). torch's own fp32 index arithmetic, so the taps (i0, i1) are torch's. The weight l1 = f - (float)i0
+// with f = s * (float)o has two legal roundings: from the rounded product (a host build, torch on the CPU) or, when the compiler
+// contracts the product into the subtraction (hipcc's default for gfx950: v_mul, v_cvt, then v_fma l1 = s*o - i0), from the exact one.
+// They differ by up to half an ulp of f (1.5e-5 at column 260). The exchange kernels -- bl_tap here, the forward copies in upcat.hip and
+// fuse.hip -- leave that choice to the compiler, instance by instance, and their tests accept exactly these two weights
+// (tests/exchange_cases.py); cseg_ms_fuse.h pins it for the test-phase kernel. DESIGN.md section 26 says what lives here and what must
+// not: indices, adjoint weights, loop nests -- never the value blends.
 #pragma once
 #include "cseg_common.h"
 

@@ -60,9 +60,9 @@ __global__ __launch_bounds__(256) void fuse_sum_kernel(FuseArgs a, int relu, flo
                 acc[t] += ly0 * (lx0 * r0[x0] + lx1 * r0[x1]) + ly1 * (lx0 * r1[x0] + lx1 * r1[x1]);
             }
         }
-        if (relu) {
+        if (relu) {                                // NaN-propagating like torch's clamp and bn.hip (fmaxf would turn a NaN into 0)
 #pragma unroll
-            for (int t = 0; t < V; ++t) acc[t] = fmaxf(acc[t], 0.f);
+            for (int t = 0; t < V; ++t) acc[t] = acc[t] < 0.f ? 0.f : acc[t];
         }
         if (VEC) *reinterpret_cast<float4*>(out + off) = make_float4(acc[0], acc[1 % V], acc[2 % V], acc[3 % V]);
         else out[off] = acc[0];

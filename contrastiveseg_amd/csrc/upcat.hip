@@ -179,6 +179,16 @@ extern "C" int cseg_upcat_fwd_amax(const float* const* xs, const int* C, const i
     return upcat_fwd_impl(xs, C, hs, ws, n_maps, B, out, amax, stream);
 }
 
+// Which kernel the adjoint of a (hs, ws) -> (h0, w0) upsampling runs on, for cseg_upcat_bwd and cseg_fuse_sum_bwd alike: 0 = gather, or the
+// tap count of the band instance (8, 12, 24, 40). Launches nothing.
+extern "C" int cseg_bilinear_adjoint_plan(int hs, int ws, int h0, int w0, int* taps, int* rows, long* lds_bytes) {
+    const BilinearAdjointPlan p = bilinear_adjoint_plan(hs, ws, h0, w0);
+    if (taps) *taps = p.taps;
+    if (rows) *rows = p.nY_max;
+    if (lds_bytes) *lds_bytes = (long)p.lds;
+    return p.route;
+}
+
 extern "C" int cseg_upcat_bwd(const float* d_out, const int* C, const int* hs, const int* ws, int n_maps, int B,
                               float* const* d_xs, cseg_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;

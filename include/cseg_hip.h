@@ -185,6 +185,11 @@ int cseg_upcat_fwd_amax(const float* const* xs, const int* C, const int* hs, con
                         float* out, unsigned* amax, cseg_stream_t stream);
 int cseg_upcat_bwd(const float* d_out, const int* C, const int* hs, const int* ws, int n_maps, int B,
                    float* const* d_xs, cseg_stream_t stream);
+/* Which kernel the adjoint of the (hs, ws) -> (h0, w0) upsampling runs on, in cseg_upcat_bwd and cseg_fuse_sum_bwd alike: returns 0 for
+ * the gather kernel, or the tap count of the band-kernel instance (8, 12, 24 or 40). *taps = fine columns budgeted per coarse column,
+ * *rows = fine rows budgeted per band, *lds_bytes = dynamic LDS a band needs (each may be NULL); a band is taken when ws <= 256,
+ * taps <= 40 and lds_bytes <= 64 KB. The launchers ask the same function; nothing is launched here. */
+int cseg_bilinear_adjoint_plan(int hs, int ws, int h0, int w0, int* taps, int* rows, long* lds_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * HRNet exchange unit: out = relu(sum_s same[s] + sum_l bilinear_up(low[l])), all terms with C channels.
