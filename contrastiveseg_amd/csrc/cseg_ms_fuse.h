@@ -1,7 +1,9 @@
 // The test phase's multi-scale + flip fusion kernel, one text for its two launch shapes: MsArgs, a [B,K,H,W] batch (ms_eval.hip,
 // cseg_ms_fuse_argmax), and RgArgs, images of differing sizes with packed outputs (ms_eval_ragged.hip, cseg_ms_fuse_argmax_ragged). The
 // two differ in which image and pixel a thread owns and where its byte and its fp32 column go, which is decided at compile time; the
-// taps and the class loop are the same statements, so a pixel (y, x) of a W-wide map gets the same operations from both.
+// taps and the class loop are the same statements, so a pixel (y, x) of a W-wide map gets the same operations from both. Two further
+// argument types ride on them: MsPermuted<Base> (a channel permutation on the mirrored operand, cseg_ms_fuse_argmax_perm / _ragged_perm)
+// and MsWeighted<MsArgs> (a per-pixel weight per term, cseg_ms_fuse_argmax_weighted in ms_eval.hip).
 #pragma once
 #include <type_traits>
 
@@ -60,6 +62,24 @@ template <class Args> struct ms_is_permuted : std::false_type {};
 template <class Base> struct ms_is_permuted<MsPermuted<Base>> : std::true_type {};
 static_assert(sizeof(MsPermuted<RgArgs>) + 2 * sizeof(void*) <= 4096, "the permuted ragged argument block exceeds HIP's 4 KB");
 
+// Per-pixel term weights (depth-aware fusion, segmentor/tester.py:447-475 of the reference; cseg_ms_fuse_argmax_weighted): pixel g of
+// the batch carries a bin, bins[g], and term i weighs its sum there with table[i * nbins + bin] in place of t[i].wt. Both arrays stay
+// in global memory -- n loads per pixel ahead of the class loop, from a table of at most 8 x 16 floats that lives in L1 -- so there is
+// no LDS copy and no barrier, and the early return of the threads behind the last pixel stays legal. An argument block WITH pixel
+// weights is its own type, as with MsPermuted. MS_MAX_BINS bounds nbins; a bin >= nbins reads column nbins - 1.
+constexpr int MS_MAX_BINS = 16;
+struct MsPixelWeights {
+    const uint8_t* bins;     // [B,H,W]
+    const float* table;      // [n, nbins]
+    int nbins;
+};
+template <class Base>
+struct MsWeighted : Base {
+    MsPixelWeights pw;
+};
+template <class Args> struct ms_is_weighted : std::false_type {};
+template <class Base> struct ms_is_weighted<MsWeighted<Base>> : std::true_type {};
+
 // perm[0..K) must be a permutation of 0..K-1. -> null, or what is wrong with it (entry index and value in *at, *val).
 inline const char* ms_perm_fault(const uint8_t* perm, int K, int* at, int* val) {
     bool seen[MS_MAX_K] = {};
@@ -94,12 +114,14 @@ constexpr bool MS_MIRROR_WEIGHT_FUSED = false;
 
 // MsArgs: one thread per output pixel of the batch. RgArgs: one thread per pixel of an image's border; image j owns the blocks from
 // im[j].block0 on, so the block-to-image map and every descriptor read are wave-uniform. MsPermuted<MsArgs>, MsPermuted<RgArgs>: the
-// same two with the flipped maps' classes permuted (a compile-time property of the argument type).
+// same two with the flipped maps' classes permuted (a compile-time property of the argument type). MsWeighted<MsArgs>: the batch
+// form with the term weights read per pixel.
 template <int NT, class Args>
 __global__ __launch_bounds__(256) void ms_fuse_kernel(Args A, uint8_t* __restrict__ pred, float* __restrict__ fused) {
 #pragma clang fp contract(off)
     constexpr bool ragged = std::is_base_of<RgArgs, Args>::value;
     constexpr bool permuted = ms_is_permuted<Args>::value;
+    constexpr bool weighted = ms_is_weighted<Args>::value;
     long g, HW;
     int b, p, y, x, xm;
     const MsTerm* t;
@@ -139,12 +161,13 @@ __global__ __launch_bounds__(256) void ms_fuse_kernel(Args A, uint8_t* __restric
             bl_tap(t[i].sy, t[i].h, y, y0, y1, ly[i]);
             bl_tap(t[i].sx, t[i].w, x, xa0[i], xa1[i], lxa[i]);
             bl_tap(t[i].sx, t[i].w, xm, xb0[i], xb1[i], lxb[i]);
-            if constexpr (ragged || permuted) {
+            if constexpr (ragged || permuted || weighted) {
                 // The ragged and the permuted instances must give the bits of the MsArgs instances image by image, so they state the
                 // roundings of the tap weights instead of leaving them to a second, independent choice of the optimiser; the tests
                 // compare the two bit for bit, on the GPU and on the emulation (tests/test_gpu_ms_eval_ragged.py,
                 // tests/test_emu_ms_eval_ragged.py; the permuted ones against the plain call on gathered maps,
-                // tests/test_gpu_lip_swap.py).
+                // tests/test_gpu_lip_swap.py; the weighted ones with a table that is constant per term against the plain call with
+                // those constants as scalar weights, tests/test_gpu_ms_depth.py).
                 ly[i] = ms_tap_weight<MS_PLAIN_WEIGHTS_FUSED<NT>>(t[i].sy, y, y0);
                 lxa[i] = ms_tap_weight<MS_PLAIN_WEIGHTS_FUSED<NT>>(t[i].sx, x, xa0[i]);
                 lxb[i] = ms_tap_weight<MS_MIRROR_WEIGHT_FUSED>(t[i].sx, xm, xb0[i]);
@@ -157,6 +180,13 @@ __global__ __launch_bounds__(256) void ms_fuse_kernel(Args A, uint8_t* __restric
             r0[i] = y0 * t[i].w;
             r1[i] = y1 * t[i].w;
         }
+    }
+
+    float wpx[weighted ? NT : 1];        // the weighted instances: this pixel's weight of every term
+    if constexpr (weighted) {
+        const int bin = min((int)A.pw.bins[g], A.pw.nbins - 1);
+#pragma unroll
+        for (int i = 0; i < NT; ++i) wpx[i] = i < A.n ? A.pw.table[i * A.pw.nbins + bin] : 0.f;
     }
 
     float best = 0.f;
@@ -181,7 +211,10 @@ __global__ __launch_bounds__(256) void ms_fuse_kernel(Args A, uint8_t* __restric
                     c1 = ly0 * s[r0[i] + xb1[i]] + ly1 * s[r1[i] + xb1[i]];
                     u = u + fmaf(lxb[i], c1 - c0, c0);
                 }
-                v = v + t[i].wt * u;
+                if constexpr (weighted)
+                    v = v + wpx[i] * u;
+                else
+                    v = v + t[i].wt * u;
             }
         }
         if (fused) fused[((size_t)b * A.K + k) * HW + p] = v;

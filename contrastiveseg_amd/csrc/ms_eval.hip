@@ -19,6 +19,12 @@
 //                  cseg_ms_fuse_argmax_perm: the flipped map's term becomes U(b_i)[perm[k]][y,W-1-x] -- the classes that trade places
 //                  under a mirror (left / right arm of a human-parsing set) are read from their partner's channel; instances of
 //                  their own (MsPermuted<MsArgs>), so the ones without a table compile from unchanged text.
+//                  cseg_ms_fuse_argmax_weighted (ms_test_depth, reference :426-475): the term's scalar weight becomes a per-pixel one,
+//                      v = v + table[i][bins[y,x]] * (U(a_i)[y,x] + U(b_i)[y,W-1-x])
+//                  read from global memory ahead of the class loop; instances of their own again (MsWeighted<MsArgs>).
+// lut_u16_u8       dst[i] = lut[src[i]], one thread per element: the depth bin of a pixel is a function of its uint16 disparity alone,
+//                  so the host evaluates the reference's float64 statements once over all 65 536 values and the device looks them up
+//                  (64 KB, L2-resident). No arithmetic on the device: the binning is exact by construction.
 // confusion_*      integer counts, exact. K <= 128: per-block histogram of K*K 32-bit bins in LDS, non-zero bins flushed with one
 //                  64-bit global atomic per bin and block. Above: lanes that hold runs of equal (gt, pred) pairs -- neighbouring
 //                  pixels mostly do -- are merged with a segmented scan over the wave, one global atomic per run.
@@ -27,6 +33,12 @@
 namespace {
 
 constexpr int CONF_LDS_K = 128;          // K*K*4 bytes of LDS: 64 KB at 128
+
+__global__ __launch_bounds__(256) void lut_u16_u8_kernel(const uint16_t* __restrict__ src, long n, const uint8_t* __restrict__ lut,
+                                                         uint8_t* __restrict__ dst) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = lut[src[i]];     // a uint16 indexes all of the 65 536 entries and nothing else
+}
 
 // bin of one pixel under RunningScore._fast_hist's mask, or -1
 __device__ __forceinline__ int conf_bin(const uint8_t* pred, const int64_t* target, long i, int K, int ignore_index) {
@@ -140,6 +152,61 @@ extern "C" int cseg_ms_fuse_argmax(int n_terms, const float* const* plain, const
                                    const int* ws, const float* weights, int B, int K, int H, int W, uint8_t* pred,
                                    float* fused, cseg_stream_t stream_) {
     return cseg_ms_fuse_argmax_perm(n_terms, plain, flipped, hs, ws, weights, nullptr, B, K, H, W, pred, fused, stream_);
+}
+
+extern "C" int cseg_ms_fuse_argmax_weighted(int n_terms, const float* const* plain, const float* const* flipped, const int* hs,
+                                            const int* ws, const float* weights, const uint8_t* bins, const float* table, int nbins,
+                                            int B, int K, int H, int W, uint8_t* pred, float* fused, cseg_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    CSEG_REQUIRE(n_terms >= 1 && n_terms <= MS_MAX_TERMS, "ms_fuse_argmax_weighted: n_terms = %d (1 to %d are supported)", n_terms,
+                 MS_MAX_TERMS);
+    CSEG_REQUIRE(plain && hs && ws, "ms_fuse_argmax_weighted: null term arrays");
+    CSEG_REQUIRE(B > 0 && H > 0 && W > 0, "ms_fuse_argmax_weighted: empty shape");
+    CSEG_REQUIRE(K >= 1 && K <= MS_MAX_K, "ms_fuse_argmax_weighted: K = %d classes (the prediction is one byte; 1 to %d)", K, MS_MAX_K);
+    CSEG_REQUIRE(nbins >= 1 && nbins <= MS_MAX_BINS, "ms_fuse_argmax_weighted: nbins = %d (1 to %d are supported)", nbins, MS_MAX_BINS);
+    CSEG_REQUIRE(bins, "ms_fuse_argmax_weighted: bins is null");
+    CSEG_REQUIRE(table, "ms_fuse_argmax_weighted: table is null");
+    CSEG_REQUIRE(pred || fused, "ms_fuse_argmax_weighted: both outputs (pred, fused) are null");
+    CSEG_REQUIRE((long)B * H * W < 2147483647L, "ms_fuse_argmax_weighted: %d x %d x %d output pixels do not fit 31 bits", B, H, W);
+    MsWeighted<MsArgs> A;
+    A.n = n_terms; A.B = B; A.K = K; A.H = H; A.W = W;
+    A.pw.bins = bins; A.pw.table = table; A.pw.nbins = nbins;
+    for (int i = 0; i < MS_MAX_TERMS; ++i) {
+        MsTerm& t = A.t[i];
+        t.a = nullptr; t.b = nullptr; t.h = 1; t.w = 1; t.sy = 0.f; t.sx = 0.f; t.wt = 0.f;
+        if (i >= n_terms) continue;
+        CSEG_REQUIRE(plain[i], "ms_fuse_argmax_weighted: term %d has no plain map", i);
+        CSEG_REQUIRE(hs[i] > 0 && ws[i] > 0, "ms_fuse_argmax_weighted: term %d is empty (%d x %d)", i, hs[i], ws[i]);
+        CSEG_REQUIRE((long)hs[i] * ws[i] < 2147483647L, "ms_fuse_argmax_weighted: term %d is too large (%d x %d)", i, hs[i], ws[i]);
+        // the term's weight is table[i][bin]; a scalar weight beside it would be a second factor that the reference does not have
+        CSEG_REQUIRE(!weights || weights[i] == 1.f, "ms_fuse_argmax_weighted: weights[%d] = %g (the weights come from table; pass NULL or "
+                     "ones)", i, (double)(weights ? weights[i] : 1.f));
+        t.a = plain[i];
+        t.b = flipped ? flipped[i] : nullptr;
+        t.h = hs[i]; t.w = ws[i];
+        t.sy = ac_scale(hs[i], H); t.sx = ac_scale(ws[i], W);
+        t.wt = 1.f;
+    }
+    const unsigned blocks = (unsigned)(((long)B * H * W + 255) / 256);
+#define LAUNCH(NT) hipLaunchKernelGGL((ms_fuse_kernel<NT, MsWeighted<MsArgs>>), dim3(blocks), dim3(256), 0, stream, A, pred, fused)
+    if (n_terms <= 1) LAUNCH(1);
+    else if (n_terms <= 2) LAUNCH(2);
+    else if (n_terms <= 4) LAUNCH(4);
+    else LAUNCH(8);
+#undef LAUNCH
+    CSEG_CHECK_LAUNCH("ms_fuse_kernel (weighted)");
+    return 1;
+}
+
+extern "C" int cseg_lut_u16_u8(const uint16_t* src, long n, const uint8_t* lut, uint8_t* dst, cseg_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    CSEG_REQUIRE(n >= 0 && n < 2147483648L, "lut_u16_u8: n = %ld elements (fewer than 2^31 are supported)", n);
+    if (n == 0) return 1;
+    CSEG_REQUIRE(src && lut && dst, "lut_u16_u8: null pointer");
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(lut_u16_u8_kernel, dim3(blocks), dim3(256), 0, stream, src, n, lut, dst);
+    CSEG_CHECK_LAUNCH("lut_u16_u8_kernel");
+    return 1;
 }
 
 extern "C" int cseg_confusion_update(const uint8_t* pred, const int64_t* target, long N, int K, int ignore_index,

@@ -1132,18 +1132,49 @@ def _perm_table(perm, K, what):
 
 
 @torch.no_grad()
-def ms_fuse_argmax(terms, H, W, want_fused=False, want_pred=True, perm=None):
+def lut_u16_u8(src, lut):
+    """dst = lut[src] on the device: src any shape, uint16 (or int16 carrying the same bits), lut u8 [65536] -> u8 of src's shape.
+    The depth bins of ms_fuse_argmax(pixel_weights=...) from a disparity map (csrc/ms_eval.hip)."""
+    if src.dtype not in (torch.uint16, I16):
+        raise RuntimeError("lut_u16_u8: src must be torch.uint16 (or int16 with the same bits), got %s" % src.dtype)
+    if lut.numel() != 65536:
+        raise RuntimeError("lut_u16_u8: lut has %d entries, expected 65536" % lut.numel())
+    src = src.contiguous()
+    dst = torch.empty(src.shape, dtype=U8, device=src.device)
+    _hip.call("cseg_lut_u16_u8", _p(src, src.dtype, "src"), src.numel(), _p(lut, U8, "lut"), _pf(dst), _hip.stream_ptr())
+    return dst
+
+
+@torch.no_grad()
+def ms_fuse_argmax(terms, H, W, want_fused=False, want_pred=True, perm=None, pixel_weights=None):
     """segmentor/tester.py:310-327, 380-398 + the argmax of :189 without any [B,K,H,W] tensor. `terms` is a list of
     (plain, flipped or None, weight): plain = the net's coarse logits [B,K,h,w] at one scale, flipped = its output for the
     horizontally mirrored input. -> pred u8 [B,H,W] (first index among equal maxima), or (pred, fused) with
     fused = sum_i weight_i * (U(plain_i) + flip(U(flipped_i))) as fp32 [B,K,H,W] when want_fused (save_prob, tests);
     pred is None when want_pred is False. perm (K ints, sequence or tensor): output class k reads class perm[k] of every flipped
     map -- the left / right classes of a human-parsing set trade places under the mirror -- which equals the call on
-    flipped.index_select(1, perm), bit for bit, without the copy."""
+    flipped.index_select(1, perm), bit for bit, without the copy.
+    pixel_weights = (bins, table): bins u8 [B,H,W], table fp32 [n, nbins] on the device, 1 <= nbins <= 16 -- term i weighs its sum at
+    pixel p with table[i, bins[p]] (the depth-aware fusion of the reference's ms_test_depth, :426-475; a bin >= nbins reads the last
+    column). Every term's scalar weight must then be 1.0 and perm None."""
     n = len(terms)
     if n < 1 or n > MS_MAX_TERMS:
         raise RuntimeError("ms_fuse_argmax: %d terms (1 to %d are supported)" % (n, MS_MAX_TERMS))
     B, K = terms[0][0].shape[:2]
+    if pixel_weights is not None:
+        if perm is not None:
+            raise RuntimeError("ms_fuse_argmax: perm together with pixel_weights: the weighted kernel takes no channel permutation")
+        for i, term in enumerate(terms):
+            if float(term[2]) != 1.0:
+                raise RuntimeError("ms_fuse_argmax: terms[%d] has weight %r together with pixel_weights: the table is the weight, "
+                                   "every scalar weight must be 1.0" % (i, term[2]))
+        bins, table = pixel_weights
+        if bins.dim() != 3 or tuple(bins.shape) != (B, int(H), int(W)):
+            raise RuntimeError("ms_fuse_argmax: pixel_weights bins is %s, expected [%d, %d, %d]" % (tuple(bins.shape), B, int(H), int(W)))
+        if table.dim() != 2 or table.shape[0] != n:
+            raise RuntimeError("ms_fuse_argmax: pixel_weights table is %s, expected [%d, nbins] (one row per term)"
+                               % (tuple(table.shape), n))
+        weighted = (_p(bins, U8, "pixel_weights bins"), _p(table, F32, "pixel_weights table"), int(table.shape[1]))
     keep, pa, pb = [], (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
     hs, ws, wt = (ctypes.c_int * n)(), (ctypes.c_int * n)(), (ctypes.c_float * n)()
     for i, (a, b, w) in enumerate(terms):
@@ -1164,7 +1195,9 @@ def ms_fuse_argmax(terms, H, W, want_fused=False, want_pred=True, perm=None):
     pred = torch.empty(B, int(H), int(W), dtype=U8, device=dev) if want_pred else None
     fused = torch.empty(B, K, int(H), int(W), dtype=F32, device=dev) if want_fused else None
     outs = (_pf(pred) if want_pred else _null(), _pf(fused) if want_fused else _null(), _hip.stream_ptr())
-    if perm is None:
+    if pixel_weights is not None:
+        _hip.call("cseg_ms_fuse_argmax_weighted", n, pa, pb, hs, ws, wt, *weighted, B, K, int(H), int(W), *outs)
+    elif perm is None:
         _hip.call("cseg_ms_fuse_argmax", n, pa, pb, hs, ws, wt, B, K, int(H), int(W), *outs)
     else:
         _hip.call("cseg_ms_fuse_argmax_perm", n, pa, pb, hs, ws, wt, _perm_table(perm, K, "ms_fuse_argmax"), B, K, int(H), int(W),

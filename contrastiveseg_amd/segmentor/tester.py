@@ -1,6 +1,6 @@
 """Test phase with the reference's surface (segmentor/tester.py:56-523: `Tester(configer).test()`, `ss_test`, `ms_test`, `sscrop_test`,
-`mscrop_test`) and config keys (test.mode, test.scale_search, optional test.scale_weights, test.crop_size, test.batch_size,
-test.out_dir, test.save_prob, network.resume).
+`mscrop_test`, `ms_test_depth`) and config keys (test.mode, test.scale_search, optional test.scale_weights, test.crop_size,
+test.batch_size, test.out_dir, test.save_prob, network.resume; test.depth_dir is this project's own).
 
 What the reference does per scale -- upsample two coarse logit maps to the input size, flip one, add, scale, accumulate into a
 [B,K,H,W] tensor (:310-327, :380-398), then move everything to the host for the argmax (:169-189) -- is linear up to the argmax.
@@ -26,7 +26,18 @@ test.flip_swap_pair (this project's own key, like contrast.use_ohem; absent by d
 class pairs that trade places under the mirror (LIP: left / right arm, leg, shoe). The mirrored pass of ms_test is then read through
 that channel permutation inside the scoring kernel (kernels.ms_fuse_argmax(perm=...)); the sliding-crop modes refuse the key.
 
-Outside the accelerated path, refused by name: ms_test_depth, crf_ss_test, the offset path; align_method scale_and_pad / only_scale
+ms_test_depth (:426-482, the recipe of configs/cityscapes/H_48_D_4_TEST_DEPTH.json): ms_test with flips whose per-scale weight is
+per PIXEL, 0.8 ** |bin - index of the scale|, the bin coming from the image's uint16 disparity PNG. The reference's float64 numpy
+statements are evaluated once per Tester over the whole uint16 domain (depth_fusion_tables): a byte table of 65 536 bins and an fp32
+table [scales, bins]. Per batch the disparity maps <test.depth_dir>/<name>.png are placed at each image's pad_offset in a zero
+uint16 [B,H,W] buffer (disparity 0 = infinitely far, as the reference's division by zero gives), uploaded once, binned by
+kernels.lut_u16_u8 and handed to kernels.ms_fuse_argmax(pixel_weights=...); no weight map and no [B,K,H,W] tensor exists.
+test.depth_dir replaces the reference's hard-coded stereo paths (:450-453); the mode is refused without it, under size_mode
+diverse_size (the reference raises on list inputs, :444-445) and together with test.flip_swap_pair. test.scale_weights is not read,
+as in the reference. A disparity map of another size than the image is refused: the reference's cv2.resize of the weight map (:471)
+is the identity only for equal sizes, and it is not approximated.
+
+Outside the accelerated path, refused by name: crf_ss_test, the offset path; align_method scale_and_pad / only_scale
 (border_size is scaled there and the final cubic resize is a real one) and size_mode max_size / multi_size; under diverse_size a
 pad_mode other than an explicit pad_right_down (the reference's crop at :180 is top-left, so only right / down padding makes its
 result the image's prediction; an absent key means `random`, collate.py:114) and the sliding-crop modes (the reference does not
@@ -43,9 +54,10 @@ from contrastiveseg_amd.lib.metrics.running_score import RunningScore
 from contrastiveseg_amd.lib.utils.distributed import get_rank
 from contrastiveseg_amd.lib.utils.tools.logger import Logger as Log
 
-SUPPORTED_MODES = ('ss_test', 'ms_test', 'sscrop_test', 'mscrop_test')
+SUPPORTED_MODES = ('ss_test', 'ms_test', 'sscrop_test', 'mscrop_test', 'ms_test_depth')
 CROP_MODES = ('sscrop_test', 'mscrop_test')
-REFUSED_MODES = ('ms_test_depth', 'crf_ss_test')
+REFUSED_MODES = ('crf_ss_test',)
+DEPTH_MAX, DEPTH_POWER_BASE = 63, 0.8      # MAX_DEPTH, POWER_BASE of the reference's fuse_with_depth (:448-449)
 
 
 def check_config(configer):
@@ -59,10 +71,11 @@ def check_config(configer):
             raise NotImplementedError('test.mode {!r} is outside the accelerated test phase; supported: {}'
                                       .format(mode, SUPPORTED_MODES))
         raise NotImplementedError('test.mode {!r} is not a test mode; supported: {}'.format(mode, SUPPORTED_MODES))
+    resolve_depth_dir(configer, mode)
     scales, weights = [1.0], None
-    if mode in ('ms_test', 'mscrop_test'):
+    if mode in ('ms_test', 'mscrop_test', 'ms_test_depth'):
         scales = list(configer.get('test', 'scale_search')) if configer.exists('test', 'scale_search') else [1.0]
-        # (mscrop_test takes no weights: reference :511-522)
+        # (mscrop_test takes no weights: reference :511-522; ms_test_depth neither: :434-441)
         if mode == 'ms_test' and configer.exists('test', 'scale_weights') and configer.get('test', 'scale_weights') is not None:
             weights = list(configer.get('test', 'scale_weights'))
             if len(weights) != len(scales):
@@ -77,6 +90,9 @@ def check_config(configer):
                                       'implemented (the final resize to the original size is the identity there; it is not '
                                       'approximated)'.format(dt))
         if dt.get('size_mode', 'fix_size') == 'diverse_size':
+            if mode == 'ms_test_depth':
+                raise NotImplementedError('test.mode {!r} under test.data_transformer size_mode diverse_size: the depth-aware fusion '
+                                          'takes batches of equal-sized images only, as in the reference'.format(mode))
             if mode in CROP_MODES:
                 raise NotImplementedError('test.mode {!r} under test.data_transformer size_mode diverse_size: the sliding-crop modes do '
                                           'not support images of differing sizes, as in the reference'.format(mode))
@@ -101,6 +117,9 @@ def flip_swap_perm(configer, mode=None):
         mode = configer.get('test', 'mode') if configer.exists('test', 'mode') else 'ss_test'
     if mode in CROP_MODES:
         raise NotImplementedError('test.flip_swap_pair together with test.mode {!r}: the sliding-crop kernel takes no channel '
+                                  'permutation; use ss_test / ms_test'.format(mode))
+    if mode == 'ms_test_depth':
+        raise NotImplementedError('test.flip_swap_pair together with test.mode {!r}: the depth-weighted kernel takes no channel '
                                   'permutation; use ss_test / ms_test'.format(mode))
     n = configer.get('data', 'num_classes')
     perm = list(range(n))
@@ -143,6 +162,55 @@ def resolve_crop_size(configer, mode):
     return int(crop[0]), int(crop[1])
 
 
+def resolve_depth_dir(configer, mode):
+    """test.depth_dir of ms_test_depth -- this project's own key in place of the reference's hard-coded stereo paths (:450-453): the
+    directory of the uint16 disparity PNGs, <depth_dir>/<name>.png -- or None for the other modes."""
+    if mode != 'ms_test_depth':
+        return None
+    depth_dir = configer.get('test', 'depth_dir') if configer.exists('test', 'depth_dir') else None
+    if depth_dir is None:
+        raise NotImplementedError('test.mode {!r} needs test.depth_dir = the directory of the uint16 disparity PNGs; it is not set'
+                                  .format(mode))
+    if not isinstance(depth_dir, str) or not depth_dir:
+        raise ValueError('test.depth_dir {!r}: expected a directory name'.format(depth_dir))
+    return depth_dir
+
+
+def depth_fusion_tables(scales):
+    """The depth arithmetic of the reference's fuse_with_depth (:459-470), its float64 numpy statements evaluated over every uint16
+    disparity value -> (lut uint8 [65536], table float32 [S, nbins]): lut[s] is the depth bin of disparity s, table[i, b] the weight
+    float32(0.8 ** |b - idx(i)|) of scale i in bin b, idx(i) the FIRST index j with scales[j] == scales[i] (_locate_scale_index,
+    :477-482). Disparity 0 divides by zero: inf, clipped to 63, the last bin. This is the only place the arithmetic lives; the device
+    looks both tables up."""
+    S = len(scales)
+    if not 1 <= S <= K.MS_MAX_TERMS:
+        raise ValueError('{} scales; 1 to {} are supported'.format(S, K.MS_MAX_TERMS))
+    stereo_map = np.arange(65536, dtype=np.uint16)
+    with np.errstate(divide='ignore'):
+        depth_map = stereo_map / 256.0
+        depth_map = 0.5 / depth_map
+        depth_map = 500 * depth_map
+    depth_map = np.clip(depth_map, 0, DEPTH_MAX)
+    depth_map = depth_map // (DEPTH_MAX // S)
+    nbins = int(depth_map.max()) + 1
+    table = np.empty((S, nbins), dtype=np.float32)
+    for i, scale in enumerate(scales):
+        scale_index = next((j for j, s in enumerate(scales) if s == scale), 0)
+        weight_map = np.abs(np.arange(nbins, dtype=np.float64) - scale_index)
+        table[i] = np.power(DEPTH_POWER_BASE, weight_map)           # float64 -> float32, the reference's .type(FloatTensor)
+    return depth_map.astype(np.uint8), table
+
+
+def load_disparity(path):
+    """-> the uint16 [h, w] array of a single-channel 16-bit PNG (cv2.imread(path, -1) of the reference, :459); anything else is
+    refused by name."""
+    from PIL import Image
+    with Image.open(path) as img:
+        if not img.mode.startswith('I;16'):
+            raise ValueError('{}: a disparity map must be a single-channel 16-bit image, this one has mode {!r}'.format(path, img.mode))
+        return np.asarray(img).astype(np.uint16, copy=False)
+
+
 def check_canvas(input_size, crop, scale):
     """-> the canvas (int(H * scale), int(W * scale)) of one sliding-crop scale; ValueError when a crop does not fit into it (the
     reference runs into an IndexError there)."""
@@ -179,6 +247,7 @@ class Tester(object):
         self.mode, self.scales, self.weights = check_config(configer)
         self.crop_size = resolve_crop_size(configer, self.mode)
         self.perm = flip_swap_perm(configer, self.mode)
+        self.depth_dir = resolve_depth_dir(configer, self.mode)
         if self.mode == 'mscrop_test' and configer.exists('test', 'scale_weights') and configer.get('test', 'scale_weights') is not None:
             Log.warn('test.scale_weights is ignored in mscrop_test, as in the reference')
         from contrastiveseg_amd.lib.models.model_manager import ModelManager
@@ -200,6 +269,11 @@ class Tester(object):
         self.running_score = RunningScore(configer, ignore_index=-1)
         self.lut = dataset_id_lut(configer)
         self.last_miou = None
+        self.depth_tables = self.depth_lut = self.depth_table = None
+        if self.mode == 'ms_test_depth':                   # once per Tester: host tables, device copies
+            self.depth_tables = depth_fusion_tables(self.scales)
+            self.depth_lut = torch.from_numpy(self.depth_tables[0]).to(self.device)
+            self.depth_table = torch.from_numpy(self.depth_tables[1]).to(self.device)
 
     # ------------------------------------------------------------------------------------------------------
     def _coarse(self, x):
@@ -267,6 +341,43 @@ class Tester(object):
             terms.append((a, b, 1.0 if self.weights is None else self.weights[i]))
         return self._fuse(terms, inputs, want_fused)
 
+    def _disparity(self, names, size, borders, pad_offsets):
+        """uint16 [B,H,W]: every image's disparity map at its pad_offset (left, up); zero -- infinitely far -- in the padding."""
+        H, W = size
+        stereo = np.zeros((len(names), H, W), dtype=np.uint16)
+        for k, name in enumerate(names):
+            bh, bw = (H, W) if borders is None else (int(borders[k][0]), int(borders[k][1]))
+            x0, y0 = (0, 0) if pad_offsets is None else (int(pad_offsets[k][0]), int(pad_offsets[k][1]))
+            path = os.path.join(self.depth_dir, '{}.png'.format(name))
+            disp = load_disparity(path)
+            if disp.shape != (bh, bw):
+                raise ValueError('{}: the disparity map is {} x {}, the image {} x {}; the reference resizes the weight map with '
+                                 'cv2.resize, which is the identity only for equal sizes and is not approximated'
+                                 .format(path, disp.shape[0], disp.shape[1], bh, bw))
+            stereo[k, y0:y0 + bh, x0:x0 + bw] = disp
+        return stereo
+
+    @torch.no_grad()
+    def ms_test_depth(self, inputs, names, want_fused=False, borders=None, pad_offsets=None):
+        """reference :426-475 + the argmax: the forwards of ms_test with flips, the per-scale weight per pixel from the disparity maps
+        <test.depth_dir>/<name>.png. borders [(h, w)] and pad_offsets [(left, up)] per image say where the unpadded image lies in the
+        input (default: all of it). One upload, kernels.lut_u16_u8, one kernels.ms_fuse_argmax(pixel_weights=...)."""
+        self.seg_net.eval()
+        if self.depth_table is None:
+            raise RuntimeError('ms_test_depth on a Tester of test.mode {!r}: the depth tables are built for ms_test_depth'
+                               .format(self.mode))
+        if isinstance(inputs, (list, tuple)):
+            raise NotImplementedError('ms_test_depth takes a batch of equal-sized images, not a list, as in the reference')
+        if len(names) != inputs.shape[0]:
+            raise ValueError('{} names for {} images'.format(len(names), inputs.shape[0]))
+        h, w = inputs.shape[-2:]
+        stereo = self._disparity(names, (h, w), borders, pad_offsets)          # before the first forward pass
+        mirrored = torch.flip(inputs, dims=[3])
+        terms = [(self._coarse(self._scaled(inputs, scale)), self._coarse(self._scaled(mirrored, scale)), 1.0) for scale in self.scales]
+        # (int16 carries the bits; the look-up reads them as uint16)
+        bins = K.lut_u16_u8(torch.from_numpy(stereo.view(np.int16)).to(self.device), self.depth_lut)
+        return K.ms_fuse_argmax(terms, h, w, want_fused=want_fused, pixel_weights=(bins, self.depth_table))
+
     def _crop_stack(self, scaled, crop):
         """The coarse outputs of the net on the reference's tiles of `scaled`, height-major (:364-373) -> [ny*nx,B,K,hc,wc]."""
         ch, cw = crop
@@ -313,7 +424,12 @@ class Tester(object):
         h, w = inputs.shape[-2:]
         return K.crop_fuse_argmax(terms, h, w, want_fused=want_fused)
 
-    def _predict(self, inputs, borders=None):
+    def _predict(self, inputs, borders=None, batch=None):
+        if self.mode == 'ms_test_depth':
+            if batch is None or isinstance(inputs, (list, tuple)):      # check_config has refused size_mode diverse_size
+                raise NotImplementedError('test.mode ms_test_depth on a list batch: images of differing sizes are not supported')
+            return self.ms_test_depth(inputs, batch['name'], self.save_prob, [(bh, bw) for bw, bh in batch['border_size']],
+                                      batch.get('pad_offset'))
         if isinstance(inputs, (list, tuple)):              # check_config has refused the sliding-crop modes
             if self.mode == 'ms_test':
                 return self.ms_test(inputs, self.save_prob, borders=borders)
@@ -382,7 +498,7 @@ class Tester(object):
                 continue
             if inputs.device != self.device:
                 inputs = inputs.to(self.device, non_blocking=True)
-            out = self._predict(inputs)
+            out = self._predict(inputs, batch=batch)
             pred, fused = out if self.save_prob else (out, None)
             labels = batch.get('labelmap')
             if labels is not None:

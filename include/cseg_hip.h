@@ -822,6 +822,20 @@ int cseg_ms_fuse_argmax(int n_terms, const float* const* plain, const float* con
 int cseg_ms_fuse_argmax_perm(int n_terms, const float* const* plain, const float* const* flipped, const int* hs, const int* ws,
                              const float* weights, const uint8_t* perm, int B, int K, int H, int W, uint8_t* pred, float* fused,
                              cseg_stream_t stream);
+/* The fusion with a per-pixel weight per term (segmentor/tester.py:426-475, ms_test_depth / fuse_with_depth: the weight of a scale
+ * depends on the pixel's depth bin). bins [B,H,W] u8 and table [n_terms, nbins] f32 are DEVICE arrays, 1 <= nbins <= 16:
+ *   v = v + table[i * nbins + min(bins[b,y,x], nbins - 1)] * (U(plain[i])[y,x] + U(flipped[i])[y,W-1-x])
+ * in the order and with the roundings of cseg_ms_fuse_argmax: with table[i][.] constant = c_i it writes the bits of that call with
+ * weights[i] = c_i, whatever bins holds. weights: NULL, or n_terms ones (anything else is refused: the table is the weight).
+ * Refused, each naming the argument, with nothing launched: n_terms outside 1..8, K outside 1..256, nbins outside 1..16, a NULL bins or
+ * table, both outputs NULL. There is no ragged and no permuted form. */
+int cseg_ms_fuse_argmax_weighted(int n_terms, const float* const* plain, const float* const* flipped, const int* hs, const int* ws,
+                                 const float* weights, const uint8_t* bins, const float* table, int nbins, int B, int K, int H, int W,
+                                 uint8_t* pred, float* fused, cseg_stream_t stream);
+/* dst[i] = lut[src[i]] for i < n: src [n] u16, lut [65536] u8, dst [n] u8, all DEVICE arrays; n < 2^31, n == 0 is a successful no-op.
+ * The depth bins of cseg_ms_fuse_argmax_weighted from a uint16 disparity map: the table is evaluated on the host in float64 over the
+ * whole uint16 domain, so the device does no depth arithmetic. */
+int cseg_lut_u16_u8(const uint16_t* src, long n, const uint8_t* lut, uint8_t* dst, cseg_stream_t stream);
 int cseg_confusion_update(const uint8_t* pred, const int64_t* target, long N, int K, int ignore_index, int64_t* confusion,
                           cseg_stream_t stream);
 
