@@ -1205,6 +1205,40 @@ def ms_fuse_argmax(terms, H, W, want_fused=False, want_pred=True, perm=None, pix
     return (pred, fused) if want_fused else pred
 
 
+@torch.no_grad()
+def cubic_argmax(seg, H, W, crop=None, flipped=None, perm=None, want_fused=False, want_pred=True, path=0):
+    """segmentor/tools/evaluator/standard.py:75-103 without the host: cv2's float INTER_CUBIC of the coarse logits seg [B,K,h,w] to
+    H x W with the argmax, no [B,K,H,W] tensor (csrc/cubic_eval.hip; the rule is stated there and in include/cseg_hip.h).
+    crop = (ch, cw): the top-left region of every map that is resized (the reference's [:border_h, :border_w]); None = the whole map.
+    flipped: the net's output for the mirrored input, seg's shape -- the value resized is (seg + flip(flipped[:, perm], [3])) / 2.,
+    the mirror over the map's full width (reference trainer :335-346); perm (K ints, sequence or tensor) needs flipped.
+    -> pred u8 [B,H,W] (first index among equal maxima), or (pred, fused) with the fp32 [B,K,H,W] resized map when want_fused; pred is
+    None when want_pred is False. path: 0 = the library's choice, 1 = direct, 2 = tiled (H >= 2 ch and W >= 2 cw); same bits."""
+    if seg.dim() != 4:
+        raise RuntimeError("cubic_argmax: seg is %s, expected [B, K, h, w]" % (tuple(seg.shape),))
+    B, K, h, w = seg.shape
+    if crop is None:
+        crop = (h, w)
+    if len(crop) != 2:
+        raise RuntimeError("cubic_argmax: crop is %r, expected (ch, cw)" % (crop,))
+    seg = seg.contiguous()
+    pb = _null()
+    if flipped is not None:
+        if flipped.shape != seg.shape:
+            raise RuntimeError("cubic_argmax: flipped is %s, seg %s" % (tuple(flipped.shape), tuple(seg.shape)))
+        flipped = flipped.contiguous()
+        pb = _p(flipped, F32, "flipped")
+    elif perm is not None:
+        raise RuntimeError("cubic_argmax: perm was given without flipped, the mirrored operand whose classes it permutes")
+    table = _perm_table(perm, K, "cubic_argmax") if perm is not None else _null()
+    pa = _p(seg, F32, "seg")
+    pred = torch.empty(B, int(H), int(W), dtype=U8, device=seg.device) if want_pred else None
+    fused = torch.empty(B, K, int(H), int(W), dtype=F32, device=seg.device) if want_fused else None
+    _hip.call("cseg_cubic_argmax", pa, pb, table, B, K, h, w, int(crop[0]), int(crop[1]), int(H), int(W), int(path),
+              _pf(pred) if want_pred else _null(), _pf(fused) if want_fused else _null(), _hip.stream_ptr())
+    return (pred, fused) if want_fused else pred
+
+
 RaggedScores = collections.namedtuple("RaggedScores", ["pred", "preds", "fused", "fuseds"])
 
 

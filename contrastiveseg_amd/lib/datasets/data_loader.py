@@ -160,7 +160,8 @@ class SyntheticRawSource(object):
 
 class GPUAugLoader(object):
     """Iterable of {'img': f32 [B,3,H,W], 'labelmap': i64 [B,H,W]} batches on `device`. Raw batch k+1 is decoded and
-    uploaded (pinned memory, side stream) while the caller trains on batch k."""
+    uploaded (pinned memory, side stream) while the caller trains on batch k. The 'val' loader under val.score_resize 'cubic' adds
+    'ori_labelmap' (a list of i64 [H_b,W_b] tensors: the label files at their own sizes) and 'border_size' ([(w, h)])."""
 
     def __init__(self, configer, source, device, split='train'):
         self.source, self.device = source, device
@@ -168,6 +169,9 @@ class GPUAugLoader(object):
         # the trainer calls `loader.sampler.set_epoch(epoch)` like the reference does (trainer_contrastive.py:183-184)
         self.sampler = source if hasattr(source, 'set_epoch') else None
         self._stream = None
+        # val.score_resize 'cubic' (segmentor/trainer_contrastive.py: score_cubic): the validation batches also carry the label files
+        # at their own sizes and the transform's border records, the reference's meta['ori_target'] and meta['border_size']
+        self.with_ori = split == 'val' and configer.exists('val', 'score_resize') and configer.get('val', 'score_resize') == 'cubic'
 
     def __len__(self):
         return len(self.source)
@@ -204,7 +208,30 @@ class GPUAugLoader(object):
                 ti.record_stream(torch.cuda.current_stream(self.device))
                 tl.record_stream(torch.cuda.current_stream(self.device))
             out = self.transform(ti, tl, sizes=sizes)
-            yield {'img': out['img'], 'labelmap': out['labelmap']}
+            batch = {'img': out['img'], 'labelmap': out['labelmap']}
+            if self.with_ori:
+                batch['ori_labelmap'] = self._ori_labels(tl, sizes)
+                batch['border_size'] = [(int(w), int(h)) for w, h in out['border_size']]
+            yield batch
+
+    def _ori_labels(self, tl, sizes):
+        """The reference's ori_target (lib/datasets/loader/default_loader.py:51-58): every raw label at the file's own size through
+        the transform's encoding table alone, 255 -> -1; no resampling, no padding. -> a list of i64 [H_b,W_b] device tensors."""
+        lut = self.transform.lut
+        if lut is not None and lut.device != tl.device:
+            lut = lut.to(tl.device)
+        if sizes is None:
+            raws = list(tl)
+        else:
+            raws, off = [], 0
+            for w, h in sizes:
+                raws.append(tl[off:off + w * h].view(h, w))
+                off += w * h
+        out = []
+        for raw in raws:
+            lab = raw.long() if lut is None else lut.long()[raw.long()]
+            out.append(torch.where(lab == 255, torch.full_like(lab, -1), lab))
+        return out
 
 
 class TestFolderLoader(object):

@@ -124,9 +124,56 @@ def score_mirrored_pair(seg, targets, hist=None, score=None):
     return score
 
 
+SCORE_RESIZES = ('bilinear', 'cubic')
+
+
+def val_score_resize(configer):
+    """val.score_resize, this project's own key: 'bilinear' (the default: upsample with align_corners=True to the transformed label,
+    the pass this trainer has always run) or 'cubic' (the reference's evaluator: cv2's float INTER_CUBIC of every image's logits to
+    the label file's own size, score_cubic). Anything else is refused, as is 'cubic' for dataset 'celeba', whose logits the
+    reference resizes to HALF the file's size (segmentor/tools/evaluator/standard.py:87-92)."""
+    mode = configer.get('val', 'score_resize') if configer.exists('val', 'score_resize') else 'bilinear'
+    if mode not in SCORE_RESIZES:
+        raise ValueError("val.score_resize {!r}: expected one of {}".format(mode, ', '.join(repr(m) for m in SCORE_RESIZES)))
+    if mode == 'cubic' and configer.exists('dataset') and configer.get('dataset') == 'celeba':
+        raise NotImplementedError("val.score_resize 'cubic' with dataset 'celeba': the reference scores celeba at half the label "
+                                  "file's size, which is not implemented")
+    return mode
+
+
+@torch.no_grad()
+def score_cubic(seg, targets, hist, borders=None, flipped=None, perm=None):
+    """One batch of the reference's StandardEvaluator.update_score (segmentor/tools/evaluator/standard.py:75-103) on the device: image
+    i's logits seg[i, :, :min(border_h, h), :min(border_w, w)] are resized with cv2's float INTER_CUBIC rule to targets[i]'s size and
+    arg-maxed by one kernel (kernels.cubic_argmax; no [K,H,W] tensor, no host copy), then counted into hist (i64 [K,K] on the device)
+    by kernels.confusion_update with ignore_index -1.
+    seg [B,K,h,w]; targets: i64 [B,H,W], or a list of B tensors [H_i,W_i] (the label files at their own sizes).
+    borders: [(border_w, border_h)] per image as the loaders record them, or None. The slice is the reference's, literally: the border
+    is in INPUT pixels while the map is coarse, so in practice it exceeds the map and crops nothing (a numpy slice beyond the end is
+    the whole axis); a border smaller than the coarse map does crop.
+    flipped, perm: the mirrored pair of the LIP pass (reference trainer :335-346) -- flipped [B,K,h,w] is the net's output for the
+    mirrored batch and what is resized is (seg + flip(flipped[:, perm], [3])) / 2., averaged at coarse size inside the kernel."""
+    B, _, h, w = seg.shape
+    n = len(targets) if isinstance(targets, (list, tuple)) else targets.shape[0]
+    if n != B:
+        raise ValueError('score_cubic: {} targets for the {} images of seg {}'.format(n, B, tuple(seg.shape)))
+    if borders is not None and len(borders) != B:
+        raise ValueError('score_cubic: {} borders for the {} images of seg {}'.format(len(borders), B, tuple(seg.shape)))
+    for i in range(B):
+        target = targets[i]
+        if target.dim() != 2:
+            raise ValueError('score_cubic: targets[{}] is {}, expected [H, W]'.format(i, tuple(target.shape)))
+        crop = (h, w) if borders is None else (min(int(borders[i][1]), h), min(int(borders[i][0]), w))
+        pred = K.cubic_argmax(seg[i:i + 1], target.shape[0], target.shape[1], crop=crop,
+                              flipped=None if flipped is None else flipped[i:i + 1], perm=perm)
+        K.confusion_update(pred, target, hist, ignore_index=-1)
+    return hist
+
+
 class Trainer(object):
     def __init__(self, configer, train_loader=None, val_loader=None):
         self.configer = configer
+        self.score_resize = val_score_resize(configer)
         self.batch_time = AverageMeter()
         self.foward_time = AverageMeter()
         self.backward_time = AverageMeter()
@@ -434,10 +481,14 @@ class Trainer(object):
 
     @torch.no_grad()
     def __val(self, data_loader=None):
-        """Validation loss + mIoU (reference :306-401 -> StandardEvaluator -> RunningScore). Logits are upsampled to the
-        label size (bilinear, align_corners=True -- the reference's evaluator resizes with cv2 INTER_CUBIC on the host,
-        which is outside the hot path), arg-maxed, and accumulated into an on-device confusion matrix with the
-        reference's RunningScore arithmetic (lib/metrics/running_score.py of this package)."""
+        """Validation loss + mIoU (reference :306-401 -> StandardEvaluator -> RunningScore). val.score_resize 'bilinear' (the
+        default): logits are upsampled to the transformed label's size (bilinear, align_corners=True), arg-maxed, and accumulated
+        into an on-device confusion matrix with the reference's RunningScore arithmetic (lib/metrics/running_score.py of this
+        package) -- a convention of this project, not the reference's number. val.score_resize 'cubic': the reference's
+        evaluator on the device (score_cubic): every image's logits, sliced [:border_h, :border_w], go through cv2's float
+        INTER_CUBIC rule to the label file's own size and the argmax in one kernel, and are scored against the batch's
+        'ori_labelmap' (the reference's ori_target; 'labelmap' where the loader yields none). The validation loss is the same in
+        both."""
         self.seg_net.eval()
         self.pixel_loss.eval()
         score = RunningScore(self.configer, ignore_index=-1)
@@ -450,11 +501,19 @@ class Trainer(object):
         # default (the branch has no earlier behaviour to keep); CSEG_VAL_FUSED=0, set explicitly, is the torch composition.
         lip = self.configer.exists('dataset') and self.configer.get('dataset') == 'lip'
         lip_fused = os.environ.get('CSEG_VAL_FUSED', '1') != '0'
+        cubic = self.score_resize == 'cubic'
         for data_dict in (self.val_loader if data_loader is None else data_loader):
             if lip:
                 (inputs, targets, inputs_rev, _), batch_size = self.data_helper.prepare_data(data_dict, want_reverse=True)
                 outputs = self.seg_net(torch.cat([inputs[0], inputs_rev[0]], dim=0), is_eval=True)
                 seg = outputs['seg'] if isinstance(outputs, dict) else outputs
+                if cubic:
+                    if hist is None:
+                        hist = torch.zeros(score.n_classes, score.n_classes, dtype=torch.int64, device=targets.device)
+                    half = seg.shape[0] // 2
+                    score_cubic(seg[:half], data_dict.get('ori_labelmap', targets), hist, borders=data_dict.get('border_size'),
+                                flipped=seg[half:], perm=lip_mirror_perm(seg.shape[1]))
+                    continue
                 if lip_fused:
                     if hist is None:
                         hist = torch.zeros(score.n_classes, score.n_classes, dtype=torch.int64, device=targets.device)
@@ -465,6 +524,12 @@ class Trainer(object):
             (inputs, targets), batch_size = self.data_helper.prepare_data(data_dict)
             outputs = self.seg_net(*inputs, is_eval=True)
             self.val_losses.update(self.pixel_loss(outputs, targets).item(), batch_size)
+            if cubic:
+                if hist is None:
+                    hist = torch.zeros(score.n_classes, score.n_classes, dtype=torch.int64, device=targets.device)
+                score_cubic(outputs['seg'] if isinstance(outputs, dict) else outputs, data_dict.get('ori_labelmap', targets), hist,
+                            borders=data_dict.get('border_size'))
+                continue
             if fused:
                 n = score.n_classes
                 if hist is None:

@@ -866,6 +866,30 @@ int cseg_ms_fuse_argmax_ragged_perm(int n_images, int n_terms, const float* cons
                                     uint8_t* pred, float* fused, cseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Validation on the reference's resize (csrc/cubic_eval.hip).  Replaces the per-image host work of
+ * segmentor/tools/evaluator/standard.py:75-103 (logits[:border_h, :border_w] -> cv2.resize(INTER_CUBIC) to the label file's size ->
+ * argmax) and, with b, the coarse-size average of the mirrored pair of segmentor/trainer_contrastive.py:335-346.
+ *
+ *   a     [B,K,h,w] f32 device pointer: the coarse logits;  (ch, cw), 1 <= ch <= h, 1 <= cw <= w: the top-left region that is resized
+ *   b     same shape, the net's output for the mirrored input, or NULL.  The value the resize reads at (r, c) is then
+ *         (a[b,k,r,c] + b[b,perm[k],r,w-1-c]) / 2.f: mirrored over the full width w, not over cw
+ *   perm  HOST array of K bytes (a permutation of the classes, as in cseg_ms_fuse_argmax_perm), or NULL for the identity
+ * The rule is cv2's float INTER_CUBIC as its scalar source states it, fp32, every product and sum rounded on its own: with
+ * scale = 1.0 / ((double)W / (double)cw) in double, f = (float)(((double)x + 0.5) * scale - 0.5), s = floor(f), t = f - (float)s
+ * (neither clamped), the interpolateCubic coefficients of t with A = -0.75f, the columns clamp(s - 1 + j, 0, cw - 1), j = 0..3 (rows
+ * likewise from H, ch), the horizontal pass hz = ((s0*c0 + s1*c1) + s2*c2) + s3*c3 per tap row and then the vertical pass
+ * v = ((hz0*d0 + hz1*d1) + hz2*d2) + hz3*d3.
+ *   pred  [B,H,W] u8, first index among equal maxima, or NULL;  fused [B,K,H,W] f32 (the value v), or NULL; not both NULL.
+ *   path  0 = the library's choice, 1 = direct (one thread per pixel, 16 global taps per class; every geometry), 2 = tiled (separable
+ *         through LDS; H >= 2 ch and W >= 2 cw).  Both write the same bits.
+ * K <= 256; B*H*W < 2^31.  Deterministic (no atomics).  Refused, each naming the argument, with nothing launched: K outside 1..256, a
+ * crop outside the map, a non-NULL perm without b or one that is no permutation, both outputs NULL, path == 2 for a geometry the tiled
+ * path does not cover, path outside 0..2.
+ * ------------------------------------------------------------------------------------------------ */
+int cseg_cubic_argmax(const float* a, const float* b, const uint8_t* perm, int B, int K, int h, int w, int ch, int cw, int H, int W,
+                      int path, uint8_t* pred, float* fused, cseg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Test phase, sliding crops (csrc/crop_eval.hip).  Replaces the tensor work of segmentor/tester.py:351-378, 505-523 (sscrop_test /
  * mscrop_test) with the argmax of :189.  Neither the [B,K,hs,ws] logits canvas nor the count canvas nor a [B,K,H,W] tensor is needed.
  *
