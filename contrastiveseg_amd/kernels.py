@@ -1387,6 +1387,82 @@ def confusion_update(pred, target, confusion, ignore_index=-1):
     return confusion
 
 
+# pixel-level Cityscapes evaluation (csrc/cityscapes_eval.hip)
+CS_LABELS = 34               # label ids 0..33: the side of the matrix
+CS_TABLE = (10, 1000, 3)     # per image: labels 24..33 x instance number x {size, tp, catTp}
+CS_CHAINS = 10               # rows of the running sums: classes 24 25 26 27 28 31 32 33, then the categories human, vehicle
+
+
+@torch.no_grad()
+def cs_eval_update(pred, lut, labelmap_raw, instancemap, records, conf):
+    """One batch of evaluatePair (lib/metrics/cityscapes_evaluator.py:559-662) up to its float arithmetic. pred u8 [B,H,W] train ids,
+    lut u8 [256] train id -> label id, labelmap_raw u8 [B,H,W] raw label ids, instancemap [B,H,W] uint16 (or int16 carrying the same
+    bits), records: B rows (x0, y0, bw, bh) on the host -- the region of every image that is scored. conf i64 [34,34] += the counts of
+    (ground truth, predicted label id), in place. -> table u32-as-i32 [B,10,1000,3] for cs_eval_reduce. A ground-truth id above 33, an
+    instance id above 1000 whose label is not one of 24..33 and a predicted label id above 33 raise, naming the first such pixel (this
+    reads four status words back: one synchronisation per call)."""
+    if pred.dim() != 3:
+        raise RuntimeError("cs_eval_update: pred is %s, expected [B, H, W]" % (tuple(pred.shape),))
+    B, H, W = pred.shape
+    for t, what in ((labelmap_raw, "labelmap_raw"), (instancemap, "instancemap")):
+        if tuple(t.shape) != (B, H, W):
+            raise RuntimeError("cs_eval_update: %s is %s, pred is %s" % (what, tuple(t.shape), (B, H, W)))
+    if instancemap.dtype not in (torch.uint16, I16):
+        raise RuntimeError("cs_eval_update: instancemap must be torch.uint16 (or int16 with the same bits), got %s" % instancemap.dtype)
+    if lut.numel() != 256:
+        raise RuntimeError("cs_eval_update: lut has %d entries, expected 256" % lut.numel())
+    if tuple(conf.shape) != (CS_LABELS, CS_LABELS):
+        raise RuntimeError("cs_eval_update: the matrix is %s, expected [%d, %d]" % (tuple(conf.shape), CS_LABELS, CS_LABELS))
+    rec = torch.as_tensor(records, dtype=I32).reshape(-1, 4).contiguous().cpu() if len(records) else torch.zeros(0, 4, dtype=I32)
+    if rec.shape[0] != B:
+        raise RuntimeError("cs_eval_update: %d records for %d images" % (rec.shape[0], B))
+    pred, labelmap_raw, instancemap = pred.contiguous(), labelmap_raw.contiguous(), instancemap.contiguous()
+    dev = pred.device
+    table = torch.zeros((B,) + CS_TABLE, dtype=I32, device=dev)
+    status = torch.zeros(4, dtype=I32, device=dev)
+    rec_dev = rec.to(dev)
+    _hip.call("cseg_cs_eval_update", _p(pred, U8, "pred"), _p(lut, U8, "lut"), _p(labelmap_raw, U8, "labelmap_raw"),
+              _p(instancemap, instancemap.dtype, "instancemap"), ctypes.c_void_p(rec.data_ptr()), _pf(rec_dev), B, H, W,
+              _p(conf, I64, "conf"), _pf(table), _pf(status), _hip.stream_ptr())
+    torch.autograd.graph.increment_version(conf)           # written through a raw pointer
+    st = [int(v) & 0xFFFFFFFF for v in status.cpu().tolist()]
+    if any(st):
+        def where(word):
+            at = 0xFFFFFFFF - word
+            return at, "image %d of the batch, row %d, column %d" % (at // (H * W), at % (H * W) // W, at % W)
+        if st[3]:
+            raise RuntimeError("cs_eval_update: the records on the device do not lie inside the %d x %d images" % (H, W))
+        if st[0]:
+            at, pos = where(st[0])
+            raise RuntimeError("cs_eval_update: labelmap_raw holds label id %d (%s); Cityscapes label ids are 0..33"
+                               % (int(labelmap_raw.view(-1)[at]), pos))
+        if st[1]:
+            at, pos = where(st[1])
+            iid = int(instancemap.view(-1)[at]) & 0xFFFF
+            raise RuntimeError("cs_eval_update: instancemap holds instance id %d (%s): label %d has no instances (labels 24..33 do)"
+                               % (iid, pos, iid // 1000))
+        at, pos = where(st[2])
+        raise RuntimeError("cs_eval_update: lut maps the prediction %d to label id %d (%s); Cityscapes label ids are 0..33"
+                           % (int(pred.view(-1)[at]), int(lut.view(-1)[int(pred.view(-1)[at])]), pos))
+    return table
+
+
+@torch.no_grad()
+def cs_eval_reduce(table, stats_i, stats_f):
+    """The float arithmetic of evaluatePair's instance loop over the table of one cs_eval_update, in the reference's order (images in
+    batch order, instance ids ascending): stats_i i64 [10,2] {tp, fn} and stats_f f64 [10,2] {tpWeighted, fnWeighted} are running
+    sums, updated in place; rows = the classes 24 25 26 27 28 31 32 33, then the categories human and vehicle."""
+    if table.dim() != 4 or tuple(table.shape[1:]) != CS_TABLE:
+        raise RuntimeError("cs_eval_reduce: table is %s, expected [B, %d, %d, %d]" % ((tuple(table.shape),) + CS_TABLE))
+    for t, what in ((stats_i, "stats_i"), (stats_f, "stats_f")):
+        if tuple(t.shape) != (CS_CHAINS, 2):
+            raise RuntimeError("cs_eval_reduce: %s is %s, expected [%d, 2]" % (what, tuple(t.shape), CS_CHAINS))
+    _hip.call("cseg_cs_eval_reduce", _p(table, I32, "table"), table.shape[0], _p(stats_i, I64, "stats_i"), _p(stats_f, F64, "stats_f"),
+              _hip.stream_ptr())
+    torch.autograd.graph.increment_version(stats_i)
+    torch.autograd.graph.increment_version(stats_f)
+
+
 # ----------------------------------------------------------------------------------------------------------
 # memory bank
 # ----------------------------------------------------------------------------------------------------------

@@ -240,7 +240,9 @@ class TestFolderLoader(object):
     get_testloader, lib/datasets/data_loader.py:205-240, yields names and metas the same way). No shuffling, no dropped or
     repeated samples: with a process group every rank takes its strided share, so that the reduced confusion matrix counts every
     image once. Under size_mode diverse_size 'img' is a list of [1,3,Hp_b,Wp_b] tensors and 'labelmap' a list of [1,Hp_b,Wp_b], every
-    image at its own size padded to fit_stride (image 0, label -1), each through the transform alone as the reference collates it."""
+    image at its own size padded to fit_stride (image 0, label -1), each through the transform alone as the reference collates it.
+    With test.evaluator set also 'labelmap_raw': u8 [B,H,W] and 'instancemap': i16 [B,H,W] (the bits of the uint16 instance ids of
+    <test.instance_dir>/<stem>.png, default <image dir>/../instance), every image at its pad_offset."""
 
     def __init__(self, configer, image_dir, label_dir, batch_size, device, workers=8):
         self.device = device
@@ -258,9 +260,47 @@ class TestFolderLoader(object):
         self.batch_size = max(1, int(batch_size))
         self.transform = GPUBatchTransform(configer, 'test')
         self.pool = ThreadPoolExecutor(max_workers=max(1, workers))
+        # test.evaluator (this project's own key): every batch additionally carries the raw label ids and the 16-bit instance ids
+        self.instance_dir = None
+        if configer.exists('test', 'evaluator') and configer.get('test', 'evaluator') is not None:
+            if self.label_dir is None:
+                raise FileNotFoundError('test.evaluator {!r} needs the raw label ids of every image under {}'
+                                        .format(configer.get('test', 'evaluator'), label_dir))
+            self.instance_dir = configer.get('test', 'instance_dir') if configer.exists('test', 'instance_dir') and configer.get(
+                'test', 'instance_dir') else os.path.join(os.path.dirname(os.path.normpath(image_dir)), 'instance')
+            for _, stem in self.items:
+                if not os.path.exists(os.path.join(self.instance_dir, stem + '.png')):
+                    raise FileNotFoundError('test.evaluator {!r}: test.instance_dir {} has no {}.png'
+                                            .format(configer.get('test', 'evaluator'), self.instance_dir, stem))
 
     def _mine(self):
         return self.items[get_rank()::get_world_size()]
+
+    def _instance(self, item, shape):
+        from contrastiveseg_amd.lib.metrics.cityscapes_score import load_instance_map
+        path = os.path.join(self.instance_dir, item[1] + '.png')
+        inst = load_instance_map(path)
+        if inst.shape != tuple(shape):
+            raise ValueError('{}: the instance map is {} x {}, the image {} x {}'.format(path, inst.shape[0], inst.shape[1], shape[0],
+                                                                                         shape[1]))
+        return inst
+
+    def _raw_maps(self, chunk, items, out):
+        """labelmap_raw u8 [B,H,W] (the label file's bytes, no label_list look-up) and instancemap i16 [B,H,W] (the 16-bit instance ids;
+        int16 carries the bits, as for the disparity maps of ms_test_depth), every image at its pad_offset, zero in the padding."""
+        B, (H, W) = len(items), out['img'].shape[-2:]
+        raw = np.zeros((B, H, W), dtype=np.uint8)
+        inst = np.zeros((B, H, W), dtype=np.uint16)
+        for k, (item, (img, lab)) in enumerate(zip(chunk, items)):
+            h, w = img.shape[:2]
+            x0, y0 = int(out['pad_offset'][k][0]), int(out['pad_offset'][k][1])
+            if (int(out['border_size'][k][0]), int(out['border_size'][k][1])) != (w, h) or lab.shape != (h, w):
+                raise ValueError('{}: the image is {} x {}, its label map {} x {} and its region in the batch {} x {}; test.evaluator '
+                                 'scores every image at its own size'.format(item[0], h, w, lab.shape[0], lab.shape[1],
+                                                                             int(out['border_size'][k][1]), int(out['border_size'][k][0])))
+            raw[k, y0:y0 + h, x0:x0 + w] = lab
+            inst[k, y0:y0 + h, x0:x0 + w] = self._instance(item, (h, w))
+        return torch.from_numpy(raw).to(self.device), torch.from_numpy(inst.view(np.int16)).to(self.device)
 
     def __len__(self):
         return (len(self._mine()) + self.batch_size - 1) // self.batch_size
@@ -314,6 +354,8 @@ class TestFolderLoader(object):
                      'pad_offset': [(int(l), int(u)) for l, u in out['pad_offset']]}
             if tl is not None:
                 batch['labelmap'] = out['labelmap']
+            if self.instance_dir is not None:
+                batch['labelmap_raw'], batch['instancemap'] = self._raw_maps(chunk, items, out)
             yield batch
 
 

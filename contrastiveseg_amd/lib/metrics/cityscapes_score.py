@@ -1,0 +1,241 @@
+"""The pixel-level Cityscapes evaluation of the reference's third stage (`python -m lib.metrics.cityscapes_evaluator`,
+lib/metrics/cityscapes_evaluator.py: EvalPixel.evaluateImgLists) fed from the device: per-class IoU, the instance-weighted iIoU
+("nIoU"), both per category, the four averages, priors and pixel accuracy.
+
+What the reference gathers per image on the host -- a 34 x 34 matrix over raw label ids, one Python tuple per pixel without its
+Cython helper, and one full-image mask per ground-truth instance -- is gathered per batch by two kernels
+(kernels.cs_eval_update / cs_eval_reduce, csrc/cityscapes_eval.hip) into three small device tensors that CityscapesScore owns:
+conf i64 [34,34], stats_i i64 [10,2] {tp, fn} and stats_f f64 [10,2] {tpWeighted, fnWeighted}, rows = the eight evaluated
+instance classes and then the categories human and vehicle. The weighted sums are sequential float64 chains in the reference's
+order (images in the order they are fed, instance ids ascending), so with one process they are the reference's bits; under a
+process group the matrix and the integer sums stay exact and the weighted sums are the sum of the ranks' chains. The scores are
+finalised on the host in float64 with the reference's statements. perImageScores is left out: the reference only ever put it
+into a JSON file whose writer is commented out.
+
+The label table and the average instance sizes are the public Cityscapes definitions (cityscapesScripts, helpers/labels.py and
+evalPixelLevelSemanticLabeling.py)."""
+import json
+import math
+import os
+from collections import OrderedDict, namedtuple
+
+import numpy as np
+import torch
+
+from contrastiveseg_amd.lib.utils import distributed as D
+
+CsLabel = namedtuple('CsLabel', ['name', 'id', 'category', 'has_instances', 'ignore_in_eval'])
+
+_VOID, _FLAT, _CONS, _OBJ, _NAT, _SKY, _HUM, _VEH = 'void', 'flat', 'construction', 'object', 'nature', 'sky', 'human', 'vehicle'
+# name, id, category, has instances, ignored in the evaluation; `license plate` has no id of its own (-1)
+LABELS = [CsLabel(*row) for row in (
+    ('unlabeled', 0, _VOID, False, True), ('ego vehicle', 1, _VOID, False, True), ('rectification border', 2, _VOID, False, True),
+    ('out of roi', 3, _VOID, False, True), ('static', 4, _VOID, False, True), ('dynamic', 5, _VOID, False, True),
+    ('ground', 6, _VOID, False, True), ('road', 7, _FLAT, False, False), ('sidewalk', 8, _FLAT, False, False),
+    ('parking', 9, _FLAT, False, True), ('rail track', 10, _FLAT, False, True), ('building', 11, _CONS, False, False),
+    ('wall', 12, _CONS, False, False), ('fence', 13, _CONS, False, False), ('guard rail', 14, _CONS, False, True),
+    ('bridge', 15, _CONS, False, True), ('tunnel', 16, _CONS, False, True), ('pole', 17, _OBJ, False, False),
+    ('polegroup', 18, _OBJ, False, True), ('traffic light', 19, _OBJ, False, False), ('traffic sign', 20, _OBJ, False, False),
+    ('vegetation', 21, _NAT, False, False), ('terrain', 22, _NAT, False, False), ('sky', 23, _SKY, False, False),
+    ('person', 24, _HUM, True, False), ('rider', 25, _HUM, True, False), ('car', 26, _VEH, True, False),
+    ('truck', 27, _VEH, True, False), ('bus', 28, _VEH, True, False), ('caravan', 29, _VEH, True, True),
+    ('trailer', 30, _VEH, True, True), ('train', 31, _VEH, True, False), ('motorcycle', 32, _VEH, True, False),
+    ('bicycle', 33, _VEH, True, False), ('license plate', -1, _VEH, False, True))]
+ID2LABEL = {lab.id: lab for lab in LABELS}
+CATEGORY2LABELS = OrderedDict()
+for _lab in LABELS:
+    CATEGORY2LABELS.setdefault(_lab.category, []).append(_lab)
+EVAL_LABELS = [lab.id for lab in LABELS if lab.id >= 0]            # every label with an id, ignored or not
+NUM_LABELS = max(EVAL_LABELS) + 1                                  # 34: the side of the matrix
+AVG_CLASS_SIZE = {'bicycle': 4672.3249222261, 'caravan': 36771.8241758242, 'motorcycle': 6298.7200839748,
+                  'rider': 3930.4788056518, 'bus': 35732.1511111111, 'train': 67583.7075812274, 'car': 12794.0202738185,
+                  'person': 3462.4756337644, 'truck': 27855.1264367816, 'trailer': 16926.9763313609}
+# rows of stats_i / stats_f: the labels with instance statistics (has instances, not ignored), then the categories whose labels
+# all have instances
+INSTANCE_CLASSES = [lab.name for lab in LABELS if lab.has_instances and not lab.ignore_in_eval]
+INSTANCE_CATEGORIES = OrderedDict(
+    (cat, [lab.id for lab in labs if lab.id >= 0]) for cat, labs in CATEGORY2LABELS.items()
+    if all(lab.has_instances for lab in labs if lab.id >= 0))
+STAT_ROWS = INSTANCE_CLASSES + list(INSTANCE_CATEGORIES)
+RESULT_FILE = os.path.join('evaluationResults', 'resultPixelLevelSemanticLabeling.json')
+assert len(STAT_ROWS) == 10 and list(INSTANCE_CATEGORIES) == [_HUM, _VEH]
+
+
+def check_label_list(label_list):
+    """data.label_list under test.evaluator cityscapes: the predictions become these ids, which index the 34 x 34 matrix."""
+    bad = [v for v in label_list if not (isinstance(v, int) and not isinstance(v, bool) and 0 <= v < NUM_LABELS)]
+    if bad:
+        raise ValueError('data.label_list holds {!r}: under test.evaluator cityscapes every entry must be a Cityscapes label id '
+                         '0..{}'.format(bad[0], NUM_LABELS - 1))
+
+
+def load_instance_map(path):
+    """-> the uint16 [h, w] array of a *_instanceIds.png (single-channel 16-bit; an 8-bit or 32-bit single-channel file whose values
+    fit is taken too, as np.array(Image.open(...)) of the reference takes it); anything else is refused by name."""
+    from PIL import Image
+    with Image.open(path) as img:
+        if not (img.mode.startswith('I') or img.mode == 'L'):
+            raise ValueError('{}: an instance map must be a single-channel integer image, this one has mode {!r}'.format(path, img.mode))
+        arr = np.asarray(img)
+    if arr.min() < 0 or arr.max() > 65535:
+        raise ValueError('{}: instance ids must lie in 0..65535, this map holds {}..{}'.format(path, arr.min(), arr.max()))
+    return arr.astype(np.uint16, copy=False)
+
+
+def _nan_or(tp, denom):
+    return float('nan') if denom == 0 else float(tp) / denom
+
+
+def finalize(conf, stats_i, stats_f):
+    """createResultDict of the reference from the matrix (34 x 34 integers) and the running sums (stats_i [10,2] integers, stats_f
+    [10,2] float64; rows = STAT_ROWS) -> (the dictionary evaluateImgLists returns, without perImageScores; pixel accuracy)."""
+    conf = np.asarray(conf).astype(np.int64)
+    if conf.shape != (NUM_LABELS, NUM_LABELS):
+        raise ValueError('the matrix is {}, expected {} x {}'.format(conf.shape, NUM_LABELS, NUM_LABELS))
+    stats_f = np.asarray(stats_f, dtype=np.float64)
+    weighted = {name: (float(stats_f[r, 0]), float(stats_f[r, 1])) for r, name in enumerate(STAT_ROWS)}
+    total = int(conf.sum())
+    kept = [l for l in EVAL_LABELS if not ID2LABEL[l].ignore_in_eval]
+
+    def col(rows, cols):
+        return int(conf[np.ix_(rows, cols)].sum()) if rows and cols else 0
+
+    class_scores, class_inst = OrderedDict(), OrderedDict()
+    for l in EVAL_LABELS:
+        lab = ID2LABEL[l]
+        fp = col([k for k in kept if k != l], [l])
+        if lab.ignore_in_eval:
+            class_scores[lab.name] = class_inst[lab.name] = float('nan')
+            continue
+        tp = int(conf[l, l])
+        fn = int(conf[l, :].sum()) - tp
+        class_scores[lab.name] = _nan_or(tp, tp + fp + fn)
+        if lab.name in INSTANCE_CLASSES:
+            tpw, fnw = weighted[lab.name]
+            class_inst[lab.name] = _nan_or(tpw, (tpw + fp) + fnw)
+        else:
+            class_inst[lab.name] = float('nan')
+    cat_scores, cat_inst = OrderedDict(), OrderedDict()
+    for cat, labs in CATEGORY2LABELS.items():
+        outside = [k for k in kept if ID2LABEL[k].category != cat]
+        ids = [lab.id for lab in labs if not lab.ignore_in_eval and lab.id in EVAL_LABELS]
+        if not ids:
+            cat_scores[cat] = float('nan')
+        else:
+            tp = col(ids, ids)
+            fn = int(conf[ids, :].sum()) - tp
+            cat_scores[cat] = _nan_or(tp, tp + col(outside, ids) + fn)
+        if cat in INSTANCE_CATEGORIES:
+            tpw, fnw = weighted[cat]
+            cat_inst[cat] = _nan_or(tpw, (tpw + col(outside, INSTANCE_CATEGORIES[cat])) + fnw)
+        else:
+            cat_inst[cat] = float('nan')
+
+    def average(scores):
+        valid, acc = 0, 0.0
+        for v in scores.values():
+            if not math.isnan(v):
+                valid += 1
+                acc += v
+        return float('nan') if valid == 0 else acc / valid
+
+    with np.errstate(divide='ignore', invalid='ignore'):
+        whole = OrderedDict()
+        whole['confMatrix'] = conf.tolist()
+        whole['priors'] = OrderedDict((ID2LABEL[l].name, float(np.float64(int(conf[l, :].sum())) / np.float64(total))) for l in EVAL_LABELS)
+        whole['labels'] = OrderedDict((ID2LABEL[l].name, l) for l in EVAL_LABELS)
+        whole['classScores'] = class_scores
+        whole['classInstScores'] = class_inst
+        whole['categoryScores'] = cat_scores
+        whole['categoryInstScores'] = cat_inst
+        whole['averageScoreClasses'] = average(class_scores)
+        whole['averageScoreInstClasses'] = average(class_inst)
+        whole['averageScoreCategories'] = average(cat_scores)
+        whole['averageScoreInstCategories'] = average(cat_inst)
+        acc = float(np.float64(int(np.diag(conf).sum())) / np.float64(total))
+    return whole, acc
+
+
+def format_tables(result, acc):
+    """The reference's two tables (printClassScores / printCategoryScores without colours), both `Score Average` lines and the pixel
+    accuracy, as a list of lines."""
+    bar = '-' * 32
+    lines = ['pixel accuracy', repr(acc), '', 'classes          IoU      nIoU', bar]
+    for l in EVAL_LABELS:
+        lab = ID2LABEL[l]
+        if not lab.ignore_in_eval:
+            lines.append('{:<14}: {:>5.6f}    {:>5.6f}'.format(lab.name, result['classScores'][lab.name], result['classInstScores'][lab.name]))
+    lines += [bar, 'Score Average : {:5.6f}    {:5.6f}'.format(result['averageScoreClasses'], result['averageScoreInstClasses']), bar, '',
+              'categories       IoU      nIoU', bar]
+    for cat, labs in CATEGORY2LABELS.items():
+        if not all(lab.ignore_in_eval for lab in labs):
+            lines.append('{:<14}: {:>5.6f}    {:>5.6f}'.format(cat, result['categoryScores'][cat], result['categoryInstScores'][cat]))
+    lines += [bar, 'Score Average : {:5.6f}    {:5.6f}'.format(result['averageScoreCategories'], result['averageScoreInstCategories']), bar]
+    return lines
+
+
+class CityscapesScore(object):
+    """Running Cityscapes scores. lut: uint8 [256], train id -> label id (Tester.lut). The tensors live on `device`; update() runs the two
+    kernels, so the device must be the GPU for it -- the tensors themselves may be filled on the host (tests, tools)."""
+
+    def __init__(self, lut, device):
+        lut = np.asarray(lut)
+        if lut.shape != (256,) or lut.dtype != np.uint8:
+            raise ValueError('lut is {} {}, expected uint8 [256]'.format(lut.dtype, lut.shape))
+        self.device = torch.device(device)
+        self.lut = torch.from_numpy(np.ascontiguousarray(lut)).to(self.device)
+        self.conf = torch.zeros(NUM_LABELS, NUM_LABELS, dtype=torch.int64, device=self.device)
+        self.stats_i = torch.zeros(len(STAT_ROWS), 2, dtype=torch.int64, device=self.device)
+        self.stats_f = torch.zeros(len(STAT_ROWS), 2, dtype=torch.float64, device=self.device)
+        self.reduced = None
+
+    def reset(self):
+        self.conf.zero_()
+        self.stats_i.zero_()
+        self.stats_f.zero_()
+        self.reduced = None
+
+    def update(self, pred, labelmap_raw, instancemap, records):
+        """pred u8 [B,H,W] train ids, labelmap_raw u8 [B,H,W], instancemap [B,H,W] (16 bits), records: B rows (x0, y0, bw, bh)."""
+        from contrastiveseg_amd import kernels as K
+        self.reduced = None
+        table = K.cs_eval_update(pred, self.lut, labelmap_raw, instancemap, records, self.conf)
+        K.cs_eval_reduce(table, self.stats_i, self.stats_f)
+
+    def reduce_scores(self):
+        """All-reduces the matrix and the sums under a process group (RunningScore.reduce_scores) -> host copies."""
+        parts = [self.conf, self.stats_i, self.stats_f]
+        if D.is_distributed() and D.get_world_size() > 1:
+            import torch.distributed as dist
+            parts = [t.cuda() if dist.get_backend() == 'nccl' and not t.is_cuda else t.clone() for t in parts]
+            for t in parts:
+                dist.all_reduce(t)
+        self.reduced = tuple(t.cpu().numpy() for t in parts)
+        return self.reduced
+
+    def results(self):
+        """-> (the reference's result dictionary, pixel accuracy)."""
+        if self.reduced is None:
+            self.reduce_scores()
+        return finalize(*self.reduced)
+
+    def inst_stats(self):
+        """The reduced sums in the shape of the reference's instStats."""
+        if self.reduced is None:
+            self.reduce_scores()
+        _, si, sf = self.reduced
+        row = lambda r: {'tp': float(si[r, 0]), 'fn': float(si[r, 1]), 'tpWeighted': float(sf[r, 0]), 'fnWeighted': float(sf[r, 1])}
+        out = {'classes': {name: row(r) for r, name in enumerate(INSTANCE_CLASSES)}, 'categories': {}}
+        for k, (cat, ids) in enumerate(INSTANCE_CATEGORIES.items()):
+            out['categories'][cat] = dict(row(len(INSTANCE_CLASSES) + k), labelIds=list(ids))
+        return out
+
+    def write_json(self, out_dir):
+        """<out_dir>/evaluationResults/resultPixelLevelSemanticLabeling.json: the result dictionary plus `pixelAccuracy`, written as the
+        reference's writeDict2JSON writes (sorted keys, indent 4; NaN as the token NaN). -> the path."""
+        result, acc = self.results()
+        path = os.path.join(out_dir, RESULT_FILE)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, 'w') as f:
+            f.write(json.dumps(dict(result, pixelAccuracy=acc), sort_keys=True, indent=4))
+        return path

@@ -37,6 +37,15 @@ diverse_size (the reference raises on list inputs, :444-445) and together with t
 as in the reference. A disparity map of another size than the image is refused: the reference's cv2.resize of the weight map (:471)
 is the identity only for equal sizes, and it is not approximated.
 
+test.evaluator: "cityscapes" (this project's own key; absent by default, and then nothing changes) adds the reference's third stage,
+`python -m lib.metrics.cityscapes_evaluator`, to the test phase: per-class and per-category IoU and instance-weighted iIoU, the four
+averages, priors and pixel accuracy (lib/metrics/cityscapes_score.py). The loader additionally yields every image's raw label ids and
+its 16-bit instance ids (<test.instance_dir>/<name>.png, default <test_dir>/../instance) at the image's pad_offset; per batch
+CityscapesScore.update runs kernels.cs_eval_update / cs_eval_reduce on the prediction that is on the device anyway; rank 0 logs the
+reference's two tables and writes <out_dir>/evaluationResults/resultPixelLevelSemanticLabeling.json. The mIoU line and last_miou stay
+as they are. Refused by name: another evaluator, size_mode diverse_size, a data.label_list with an entry outside 0..33, a missing
+label or instance directory or file, an instance map of another size than its image.
+
 Outside the accelerated path, refused by name: crf_ss_test, the offset path; align_method scale_and_pad / only_scale
 (border_size is scaled there and the final cubic resize is a real one) and size_mode max_size / multi_size; under diverse_size a
 pad_mode other than an explicit pad_right_down (the reference's crop at :180 is top-left, so only right / down padding makes its
@@ -50,6 +59,7 @@ import torch
 import torch.nn.functional as F
 
 from contrastiveseg_amd import kernels as K
+from contrastiveseg_amd.lib.metrics import cityscapes_score as CS
 from contrastiveseg_amd.lib.metrics.running_score import RunningScore
 from contrastiveseg_amd.lib.utils.distributed import get_rank
 from contrastiveseg_amd.lib.utils.tools.logger import Logger as Log
@@ -101,7 +111,67 @@ def check_config(configer):
                                           'explicitly: the prediction of a padded image is cropped top-left, so only right / down '
                                           "padding makes it the image's prediction, and an absent pad_mode means 'random'".format(dt))
     flip_swap_perm(configer, mode)
+    resolve_evaluator(configer)
     return mode, scales, weights
+
+
+EVALUATORS = ('cityscapes',)
+IMG_EXT = ('.jpg', '.jpeg', '.png', '.bmp')
+
+
+def image_dir_of(configer):
+    """test.test_dir, or <data.data_dir>/val/image as DataLoader.get_testloader resolves it; None when neither key is set."""
+    if configer.exists('test', 'test_dir') and configer.get('test', 'test_dir'):
+        return configer.get('test', 'test_dir')
+    if configer.exists('data', 'data_dir') and configer.get('data', 'data_dir'):
+        data_dir = configer.get('data', 'data_dir')
+        return os.path.join(data_dir[0] if isinstance(data_dir, (list, tuple)) else data_dir, 'val', 'image')
+    return None
+
+
+def resolve_evaluator(configer):
+    """test.evaluator -- this project's own key, like test.depth_dir: 'cityscapes' adds the pixel-level Cityscapes evaluation to the
+    test phase. -> (evaluator, instance_dir), or (None, None) without the key. Everything the mode needs is checked here, before a model
+    is built: the name, the size mode, data.label_list, and -- where the image directory is known -- the label and instance
+    directories with one file per image."""
+    name = configer.get('test', 'evaluator') if configer.exists('test', 'evaluator') else None
+    if name is None:
+        return None, None
+    if name not in EVALUATORS:
+        raise NotImplementedError('test.evaluator {!r} is not an evaluator; supported: {}'.format(name, EVALUATORS))
+    if is_ragged(configer):
+        raise NotImplementedError('test.evaluator {!r} under test.data_transformer size_mode diverse_size: the evaluation takes '
+                                  'batches of equal-sized images only'.format(name))
+    if configer.exists('data', 'label_list'):
+        CS.check_label_list(list(configer.get('data', 'label_list')))
+    elif configer.get('data', 'num_classes') > CS.NUM_LABELS:
+        raise ValueError('data.num_classes {} without data.label_list: under test.evaluator {!r} the predictions must be Cityscapes '
+                         'label ids 0..{}'.format(configer.get('data', 'num_classes'), name, CS.NUM_LABELS - 1))
+    image_dir = image_dir_of(configer)
+    instance_dir = configer.get('test', 'instance_dir') if configer.exists('test', 'instance_dir') else None
+    if instance_dir is not None and (not isinstance(instance_dir, str) or not instance_dir):
+        raise ValueError('test.instance_dir {!r}: expected a directory name'.format(instance_dir))
+    if image_dir is None or not os.path.isdir(image_dir):
+        return name, instance_dir                          # the loader names the missing image directory
+    parent = os.path.dirname(os.path.normpath(image_dir))
+    label_dir = os.path.join(parent, 'label')
+    if instance_dir is None:
+        instance_dir = os.path.join(parent, 'instance')
+    if not os.path.isdir(label_dir):
+        raise FileNotFoundError('test.evaluator {!r} needs the raw label ids of every image: the label directory {} does not exist'
+                                .format(name, label_dir))
+    if not os.path.isdir(instance_dir):
+        raise FileNotFoundError('test.evaluator {!r} needs the instance ids of every image: test.instance_dir {} does not exist'
+                                .format(name, instance_dir))
+    for fname in sorted(os.listdir(image_dir)):
+        stem, ext = os.path.splitext(fname)
+        if ext.lower() not in IMG_EXT:
+            continue
+        if not os.path.exists(os.path.join(label_dir, stem + '.png')):
+            raise FileNotFoundError('test.evaluator {!r}: the label directory {} has no {}.png'.format(name, label_dir, stem))
+        if not os.path.exists(os.path.join(instance_dir, stem + '.png')):
+            raise FileNotFoundError('test.evaluator {!r}: test.instance_dir {} has no {}.png'.format(name, instance_dir, stem))
+    return name, instance_dir
 
 
 def flip_swap_perm(configer, mode=None):
@@ -269,6 +339,9 @@ class Tester(object):
         self.running_score = RunningScore(configer, ignore_index=-1)
         self.lut = dataset_id_lut(configer)
         self.last_miou = None
+        self.evaluator = resolve_evaluator(configer)[0]
+        self.cs_score = CS.CityscapesScore(self.lut, self.device) if self.evaluator == 'cityscapes' else None
+        self.last_cityscapes = None                        # (result dictionary, pixel accuracy) of the last test()
         self.depth_tables = self.depth_lut = self.depth_table = None
         if self.mode == 'ms_test_depth':                   # once per Tester: host tables, device copies
             self.depth_tables = depth_fusion_tables(self.scales)
@@ -475,6 +548,17 @@ class Tester(object):
             Log.info('{:4d} label map generated'.format(n_img + k + 1))
         return labels is not None
 
+    def _cityscapes_update(self, pred, batch):
+        """One batch of the Cityscapes evaluation: the prediction as the scoring kernel wrote it, the loader's raw label and instance
+        maps, and every image's unpadded region (x0, y0, bw, bh)."""
+        for key in ('labelmap_raw', 'instancemap'):
+            if key not in batch:
+                raise RuntimeError('test.evaluator {!r}: the batch carries no {!r}; the test loader yields it when the key is set'
+                                   .format(self.evaluator, key))
+        offsets = batch.get('pad_offset') or [(0, 0)] * len(batch['border_size'])
+        records = [(int(x0), int(y0), int(bw), int(bh)) for (x0, y0), (bw, bh) in zip(offsets, batch['border_size'])]
+        self.cs_score.update(pred, batch['labelmap_raw'].to(self.device), batch['instancemap'].to(self.device), records)
+
     @torch.no_grad()
     def test(self, data_loader=None):
         from PIL import Image
@@ -487,12 +571,17 @@ class Tester(object):
             os.makedirs(os.path.join(self.save_dir, 'prob'), exist_ok=True)
         Log.info('save dir {}'.format(self.save_dir))
         self.running_score.reset()
+        if self.cs_score is not None:
+            self.cs_score.reset()
         K_cls = self.configer.get('data', 'num_classes')
         confusion = torch.zeros(K_cls, K_cls, dtype=torch.int64, device=self.device)
         start, n_img, scored = time.time(), 0, False
         for batch in loader:
             inputs = batch['img']
             if isinstance(inputs, (list, tuple)):
+                if self.cs_score is not None:              # check_config has refused size_mode diverse_size
+                    raise NotImplementedError('test.evaluator {!r} on a list batch: images of differing sizes are not supported'
+                                              .format(self.evaluator))
                 scored = self._test_ragged(batch, confusion, label_dir, n_img) or scored
                 n_img += len(inputs)
                 continue
@@ -505,6 +594,8 @@ class Tester(object):
                 # pixels outside an image's unpadded region carry the ignore label (-1): the loader's padding
                 K.confusion_update(pred, labels.to(self.device), confusion, ignore_index=-1)
                 scored = True
+            if self.cs_score is not None:
+                self._cityscapes_update(pred, batch)
             pred_np = pred.cpu().numpy()
             for k, name in enumerate(batch['name']):
                 bw, bh = batch['border_size'][k]
@@ -522,4 +613,11 @@ class Tester(object):
             self.last_miou = float(self.running_score.get_mean_iou())
             if get_rank() == 0:
                 Log.info('Test mIoU {:.6f}\tPixel acc {:.6f}'.format(self.last_miou, float(self.running_score.get_pixel_acc())))
+        if self.cs_score is not None:
+            self.cs_score.reduce_scores()                  # every rank: a collective under a process group
+            self.last_cityscapes = self.cs_score.results()
+            if get_rank() == 0:
+                for line in CS.format_tables(*self.last_cityscapes):
+                    Log.info(line)
+                Log.info('Cityscapes scores written to {}'.format(self.cs_score.write_json(self.save_dir)))
         return self.last_miou

@@ -1011,6 +1011,34 @@ int cseg_ohem_bwd(const float* seg, const int64_t* target, const float* weight, 
                   int W, const float* p, const float* lse, const float* out, const int32_t* outi, const float* d_loss, float* d_seg,
                   cseg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pixel-level Cityscapes evaluation of the test phase (csrc/cityscapes_eval.hip).  Replaces evaluatePair of
+ * lib/metrics/cityscapes_evaluator.py:559-662 for a batch: the 34 x 34 matrix over raw label ids and the instance-weighted sums behind
+ * iIoU ("nIoU"), with the reference's order of float64 operations.  B * H * W < 2^31 per call.
+ *
+ *   cseg_cs_eval_update  pred [B,H,W] u8 train ids, lut [256] u8 train id -> label id, labelmap_raw [B,H,W] u8 label ids,
+ *                        instancemap [B,H,W] u16 (label id, or label id * 1000 + instance number), records [B][4] i32
+ *                        {x0, y0, bw, bh}: the region of image b that is scored -- given twice, records_host for the checks made
+ *                        before the launch (a region outside the image is refused) and the same values on the device.
+ *                        conf [34,34] i64 += counts of (labelmap_raw, lut[pred]) over the regions; there is no ignore value.
+ *                        table [B,10,1000,3] u32, zero-filled by the caller: for label 24 + j and instance number n the pixels of
+ *                        instance id (24 + j) * 1000 + n > 1000 {size, pixels predicted as that label, pixels predicted inside the
+ *                        label's category ({24, 25} human, {26 .. 33} vehicle)} are added to table[b][j][n].
+ *                        status [4] u32, zero-filled by the caller; a word becomes 0xFFFFFFFF - (the smallest flat index into [B,H,W]
+ *                        of an offending pixel): [0] labelmap_raw > 33, [1] an instance id > 1000 with id / 1000 outside 24..33,
+ *                        [2] lut[pred] > 33; [3] = 1: the device records do not lie inside the image.  Offending pixels are left out
+ *                        of the output they would index.  Integer atomics: exact, independent of the order of execution.
+ *   cseg_cs_eval_reduce  table of one update -> stats_i [10][2] i64 {tp, fn} and stats_f [10][2] f64 {tpWeighted, fnWeighted}, both read
+ *                        and written back (running sums over calls): rows 0..7 the classes 24 25 26 27 28 31 32 33, row 8 human, row 9
+ *                        vehicle.  Per row: images in batch order, labels ascending, instance numbers ascending;
+ *                        weight = avgClassSize / double(size), tpWeighted += double(tp) * weight, fnWeighted += double(size - tp) *
+ *                        weight, every operation rounded on its own.  Labels 29 and 30 enter no row.  Deterministic.
+ * ------------------------------------------------------------------------------------------------ */
+int cseg_cs_eval_update(const uint8_t* pred, const uint8_t* lut, const uint8_t* labelmap_raw, const uint16_t* instancemap,
+                        const int32_t* records_host, const int32_t* records, int B, int H, int W, int64_t* conf, uint32_t* table,
+                        uint32_t* status, cseg_stream_t stream);
+int cseg_cs_eval_reduce(const uint32_t* table, int B, int64_t* stats_i, double* stats_f, cseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
