@@ -195,6 +195,7 @@ SIGNATURES = {
     "cseg_confusion_update": (_c_int, [_ptr, _ptr, ctypes.c_long, _c_int, _c_int, _ptr, _ptr]),
     "cseg_cs_eval_update": (_c_int, [_ptr] * 6 + [_c_int] * 3 + [_ptr] * 4),
     "cseg_cs_eval_reduce": (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr]),
+    "cseg_segfix_shift": (_c_int, [_ptr, _ptr, _c_int, _ptr, _ptr, _c_float, _ptr] + [_c_int] * 3 + [_ptr] * 4),
     "cseg_crop_fuse_argmax": (_c_int, [_c_int, ctypes.POINTER(_ptr), ctypes.POINTER(_ptr), ctypes.POINTER(_c_int)] + [_c_int] * 4 +
                               [_ptr, _ptr, _ptr]),
     "cseg_rmi_pool_blocks": (_c_int, [_c_int] * 4),

@@ -1463,6 +1463,38 @@ def cs_eval_reduce(table, stats_i, stats_f):
     torch.autograd.graph.increment_version(stats_f)
 
 
+@torch.no_grad()
+def segfix_shift(pred, offsets, records, scale, lut=None):
+    """shift() of scripts/cityscapes/segfix.py:64-79 for a batch, on the device (csrc/segfix.hip). pred u8 [B,H,W] train ids, offsets
+    [B,H,W,2] (row offset, column offset per pixel, as loadmat returns them) fp32 or int8 -- equal values give equal output --,
+    records: B rows (x0, y0, bw, bh) on the host -- the unpadded region of every image, refined as an image of bh x bw --, scale: the
+    factor on every offset (fp32), lut u8 [256] train id -> dataset id or None.
+    -> (refined u8 [B,H,W]: the refined train ids, pred outside the regions; refined_ids = lut[refined] or None without a lut;
+    changed i32 [B]: the pixels of every image whose label changed). No synchronisation."""
+    if pred.dim() != 3:
+        raise RuntimeError("segfix_shift: pred is %s, expected [B, H, W]" % (tuple(pred.shape),))
+    B, H, W = pred.shape
+    if tuple(offsets.shape) != (B, H, W, 2):
+        raise RuntimeError("segfix_shift: offsets is %s, expected %s for pred %s" % (tuple(offsets.shape), (B, H, W, 2), (B, H, W)))
+    if offsets.dtype not in (F32, torch.int8):
+        raise RuntimeError("segfix_shift: offsets must be torch.float32 or torch.int8, got %s" % offsets.dtype)
+    if lut is not None and lut.numel() != 256:
+        raise RuntimeError("segfix_shift: lut has %d entries, expected 256" % lut.numel())
+    rec = torch.as_tensor(records, dtype=I32).reshape(-1, 4).contiguous().cpu() if len(records) else torch.zeros(0, 4, dtype=I32)
+    if rec.shape[0] != B:
+        raise RuntimeError("segfix_shift: %d records for %d images" % (rec.shape[0], B))
+    pred, offsets = pred.contiguous(), offsets.contiguous()
+    dev = pred.device
+    refined = torch.empty_like(pred)
+    refined_ids = torch.empty_like(pred) if lut is not None else None
+    changed = torch.zeros(B, dtype=I32, device=dev)
+    rec_dev = rec.to(dev)
+    _hip.call("cseg_segfix_shift", _p(pred, U8, "pred"), _p(offsets, offsets.dtype, "offsets"), int(offsets.dtype == torch.int8),
+              ctypes.c_void_p(rec.data_ptr()), _pf(rec_dev), float(scale), _opt(lut, U8, "lut"), B, H, W, _pf(refined),
+              _pf(refined_ids) if refined_ids is not None else _null(), _pf(changed), _hip.stream_ptr())
+    return refined, refined_ids, changed
+
+
 # ----------------------------------------------------------------------------------------------------------
 # memory bank
 # ----------------------------------------------------------------------------------------------------------

@@ -242,7 +242,9 @@ class TestFolderLoader(object):
     image once. Under size_mode diverse_size 'img' is a list of [1,3,Hp_b,Wp_b] tensors and 'labelmap' a list of [1,Hp_b,Wp_b], every
     image at its own size padded to fit_stride (image 0, label -1), each through the transform alone as the reference collates it.
     With test.evaluator set also 'labelmap_raw': u8 [B,H,W] and 'instancemap': i16 [B,H,W] (the bits of the uint16 instance ids of
-    <test.instance_dir>/<stem>.png, default <image dir>/../instance), every image at its pad_offset."""
+    <test.instance_dir>/<stem>.png, default <image dir>/../instance), every image at its pad_offset. With test.segfix_offset_dir set
+    also 'segfix_offset': int8 or f32 [B,H,W,2], the boundary offsets <dir>/<stem>.mat (else .npy) of every image at its pad_offset,
+    zero in the padding (lib/datasets/segfix_offsets.py)."""
 
     def __init__(self, configer, image_dir, label_dir, batch_size, device, workers=8):
         self.device = device
@@ -273,8 +275,36 @@ class TestFolderLoader(object):
                     raise FileNotFoundError('test.evaluator {!r}: test.instance_dir {} has no {}.png'
                                             .format(configer.get('test', 'evaluator'), self.instance_dir, stem))
 
+        # test.segfix_offset_dir (this project's own key): every batch additionally carries the boundary offsets of its images
+        self.segfix_dir, self.segfix_files = None, {}
+        if configer.exists('test', 'segfix_offset_dir') and configer.get('test', 'segfix_offset_dir') is not None:
+            from contrastiveseg_amd.lib.datasets.segfix_offsets import find_offset_file
+            self.segfix_dir = configer.get('test', 'segfix_offset_dir')
+            if not isinstance(self.segfix_dir, str) or not os.path.isdir(self.segfix_dir):
+                raise FileNotFoundError('test.segfix_offset_dir {!r} does not exist'.format(self.segfix_dir))
+            if self.transform.size_mode == 'diverse_size':
+                raise NotImplementedError('test.segfix_offset_dir under test.data_transformer size_mode diverse_size: the refinement '
+                                          'takes batches of equal-sized images only')
+            for _, stem in self.items:
+                self.segfix_files[stem] = find_offset_file(self.segfix_dir, stem)
+                if self.segfix_files[stem] is None:
+                    raise FileNotFoundError('test.segfix_offset_dir {} has neither {}.mat nor {}.npy'.format(self.segfix_dir, stem, stem))
+
     def _mine(self):
         return self.items[get_rank()::get_world_size()]
+
+    def _segfix_offsets(self, chunk, items, out):
+        """int8 or f32 [B,H,W,2]: every image's offsets at its pad_offset, zero in the padding."""
+        from contrastiveseg_amd.lib.datasets.segfix_offsets import batch_offsets, load_offsets
+        regions = []
+        for k, (item, (img, _)) in enumerate(zip(chunk, items)):
+            h, w = img.shape[:2]
+            if (int(out['border_size'][k][0]), int(out['border_size'][k][1])) != (w, h):
+                raise ValueError('{}: the image is {} x {} and its region in the batch {} x {}; test.segfix_offset_dir refines every '
+                                 'image at its own size'.format(item[0], h, w, int(out['border_size'][k][1]), int(out['border_size'][k][0])))
+            regions.append((int(out['pad_offset'][k][0]), int(out['pad_offset'][k][1]), w, h))
+        arrays = list(self.pool.map(lambda a: load_offsets(self.segfix_files[a[0][1]], a[1][0].shape[:2]), zip(chunk, items)))
+        return torch.from_numpy(batch_offsets(arrays, regions, out['img'].shape[-2:])).to(self.device)
 
     def _instance(self, item, shape):
         from contrastiveseg_amd.lib.metrics.cityscapes_score import load_instance_map
@@ -356,6 +386,8 @@ class TestFolderLoader(object):
                 batch['labelmap'] = out['labelmap']
             if self.instance_dir is not None:
                 batch['labelmap_raw'], batch['instancemap'] = self._raw_maps(chunk, items, out)
+            if self.segfix_dir is not None:
+                batch['segfix_offset'] = self._segfix_offsets(chunk, items, out)
             yield batch
 
 

@@ -57,7 +57,8 @@ INSTANCE_CATEGORIES = OrderedDict(
     (cat, [lab.id for lab in labs if lab.id >= 0]) for cat, labs in CATEGORY2LABELS.items()
     if all(lab.has_instances for lab in labs if lab.id >= 0))
 STAT_ROWS = INSTANCE_CLASSES + list(INSTANCE_CATEGORIES)
-RESULT_FILE = os.path.join('evaluationResults', 'resultPixelLevelSemanticLabeling.json')
+RESULT_DIR, RESULT_NAME = 'evaluationResults', 'resultPixelLevelSemanticLabeling.json'
+RESULT_FILE = os.path.join(RESULT_DIR, RESULT_NAME)
 assert len(STAT_ROWS) == 10 and list(INSTANCE_CATEGORIES) == [_HUM, _VEH]
 
 
@@ -230,11 +231,12 @@ class CityscapesScore(object):
             out['categories'][cat] = dict(row(len(INSTANCE_CLASSES) + k), labelIds=list(ids))
         return out
 
-    def write_json(self, out_dir):
-        """<out_dir>/evaluationResults/resultPixelLevelSemanticLabeling.json: the result dictionary plus `pixelAccuracy`, written as the
-        reference's writeDict2JSON writes (sorted keys, indent 4; NaN as the token NaN). -> the path."""
+    def write_json(self, out_dir, subdir=RESULT_DIR):
+        """<out_dir>/<subdir>/resultPixelLevelSemanticLabeling.json (subdir: evaluationResults unless given; the scores of the SegFix
+        refinement go to evaluationResults_w_segfix): the result dictionary plus `pixelAccuracy`, written as the reference's
+        writeDict2JSON writes (sorted keys, indent 4; NaN as the token NaN). -> the path."""
         result, acc = self.results()
-        path = os.path.join(out_dir, RESULT_FILE)
+        path = os.path.join(out_dir, subdir, RESULT_NAME)
         os.makedirs(os.path.dirname(path), exist_ok=True)
         with open(path, 'w') as f:
             f.write(json.dumps(dict(result, pixelAccuracy=acc), sort_keys=True, indent=4))

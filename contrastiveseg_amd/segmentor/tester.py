@@ -46,6 +46,18 @@ reference's two tables and writes <out_dir>/evaluationResults/resultPixelLevelSe
 as they are. Refused by name: another evaluator, size_mode diverse_size, a data.label_list with an entry outside 0..33, a missing
 label or instance directory or file, an instance map of another size than its image.
 
+test.segfix_offset_dir (this project's own key; absent by default, and then nothing changes) with test.segfix_scale (default 2.0) adds
+the reference's second stage, scripts/cityscapes/segfix.py, to the test phase: every pixel's label moves along a precomputed
+boundary offset (<dir>/<name>.mat as the script reads it, else <dir>/<name>.npy; lib/datasets/segfix_offsets.py). The loader yields
+the offsets at each image's pad_offset, int8 where the file's integers fit; per batch one kernels.segfix_shift call (csrc/segfix.hip)
+refines the finished prediction of whatever test.mode inside every image's unpadded region -- the script's grid_sample blend of class
+INDICES, in its fp32 order, rounded half to even -- and returns the dataset ids and the number of changed pixels with it. label/ and
+the `Test mIoU` line stay as they are; the refined maps go to <out_dir>/label_w_segfix/, a second confusion matrix feeds a `Test mIoU
+(SegFix)` line, and with test.evaluator a second CityscapesScore writes evaluationResults_w_segfix/. Refused by name: size_mode
+diverse_size, a data.label_list other than the 19 Cityscapes train classes the script hard-codes, a missing directory, an image
+without an offset file, an array that is not [h, w, 2] of the image's size, non-numeric or with non-finite values. Outside: predicting
+the offsets (segfix_hrnet, tester_offset.py), segfix_instance.py and segfix_ade20k.py.
+
 Outside the accelerated path, refused by name: crf_ss_test, the offset path; align_method scale_and_pad / only_scale
 (border_size is scaled there and the final cubic resize is a real one) and size_mode max_size / multi_size; under diverse_size a
 pad_mode other than an explicit pad_right_down (the reference's crop at :180 is top-left, so only right / down padding makes its
@@ -112,11 +124,46 @@ def check_config(configer):
                                           "padding makes it the image's prediction, and an absent pad_mode means 'random'".format(dt))
     flip_swap_perm(configer, mode)
     resolve_evaluator(configer)
+    resolve_segfix(configer)
     return mode, scales, weights
 
 
 EVALUATORS = ('cityscapes',)
 IMG_EXT = ('.jpg', '.jpeg', '.png', '.bmp')
+SEGFIX_LABEL_DIR = 'label_w_segfix'                        # the reference script's directory name
+SEGFIX_RESULT_DIR = 'evaluationResults_w_segfix'
+
+
+def resolve_segfix(configer):
+    """test.segfix_offset_dir / test.segfix_scale -- this project's own keys, like test.depth_dir: the SegFix refinement of the
+    reference's scripts/cityscapes/segfix.py inside the test phase. -> (offset_dir, scale), or (None, None) without the key.
+    Everything the mode needs is checked here, before a model is built: the size mode, data.label_list, the directory, and --
+    where the image directory is known -- one offset file per image."""
+    from contrastiveseg_amd.lib.datasets import segfix_offsets as SO
+    offset_dir = configer.get('test', 'segfix_offset_dir') if configer.exists('test', 'segfix_offset_dir') else None
+    if offset_dir is None:
+        return None, None
+    if not isinstance(offset_dir, str) or not offset_dir:
+        raise ValueError('test.segfix_offset_dir {!r}: expected a directory name'.format(offset_dir))
+    scale = configer.get('test', 'segfix_scale') if configer.exists('test', 'segfix_scale') else 2.0
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not np.isfinite(scale):
+        raise ValueError('test.segfix_scale {!r}: expected a finite number'.format(scale))
+    if is_ragged(configer):
+        raise NotImplementedError('test.segfix_offset_dir under test.data_transformer size_mode diverse_size: the refinement takes '
+                                  'batches of equal-sized images only')
+    label_list = list(configer.get('data', 'label_list')) if configer.exists('data', 'label_list') else None
+    if label_list != SO.LABEL_LIST:
+        raise NotImplementedError('test.segfix_offset_dir with data.label_list {}: the refinement is the Cityscapes script of the '
+                                  'reference, which hard-codes the label list {}'.format(label_list, SO.LABEL_LIST))
+    if not os.path.isdir(offset_dir):
+        raise FileNotFoundError('test.segfix_offset_dir {} does not exist'.format(offset_dir))
+    image_dir = image_dir_of(configer)
+    if image_dir is not None and os.path.isdir(image_dir):           # (otherwise the loader names the missing image directory)
+        for fname in sorted(os.listdir(image_dir)):
+            stem, ext = os.path.splitext(fname)
+            if ext.lower() in IMG_EXT and SO.find_offset_file(offset_dir, stem) is None:
+                raise FileNotFoundError('test.segfix_offset_dir {} has neither {}.mat nor {}.npy'.format(offset_dir, stem, stem))
+    return offset_dir, float(scale)
 
 
 def image_dir_of(configer):
@@ -342,6 +389,13 @@ class Tester(object):
         self.evaluator = resolve_evaluator(configer)[0]
         self.cs_score = CS.CityscapesScore(self.lut, self.device) if self.evaluator == 'cityscapes' else None
         self.last_cityscapes = None                        # (result dictionary, pixel accuracy) of the last test()
+        self.segfix_dir, self.segfix_scale = resolve_segfix(configer)
+        self.segfix_lut = self.running_score_segfix = self.cs_score_segfix = None
+        self.last_miou_segfix = self.last_cityscapes_segfix = None             # the same two for the refined maps
+        if self.segfix_dir is not None:
+            self.segfix_lut = torch.from_numpy(self.lut).to(self.device)
+            self.running_score_segfix = RunningScore(configer, ignore_index=-1)
+            self.cs_score_segfix = CS.CityscapesScore(self.lut, self.device) if self.evaluator == 'cityscapes' else None
         self.depth_tables = self.depth_lut = self.depth_table = None
         if self.mode == 'ms_test_depth':                   # once per Tester: host tables, device copies
             self.depth_tables = depth_fusion_tables(self.scales)
@@ -548,16 +602,28 @@ class Tester(object):
             Log.info('{:4d} label map generated'.format(n_img + k + 1))
         return labels is not None
 
-    def _cityscapes_update(self, pred, batch):
-        """One batch of the Cityscapes evaluation: the prediction as the scoring kernel wrote it, the loader's raw label and instance
-        maps, and every image's unpadded region (x0, y0, bw, bh)."""
+    @staticmethod
+    def _records(batch):
+        """Every image's unpadded region (x0, y0, bw, bh) in the batch."""
+        offsets = batch.get('pad_offset') or [(0, 0)] * len(batch['border_size'])
+        return [(int(x0), int(y0), int(bw), int(bh)) for (x0, y0), (bw, bh) in zip(offsets, batch['border_size'])]
+
+    def _cityscapes_update(self, pred, batch, score=None):
+        """One batch of the Cityscapes evaluation: the prediction as the scoring kernel wrote it (score: the CityscapesScore that takes
+        it, default the unrefined one), the loader's raw label and instance maps, and every image's unpadded region."""
         for key in ('labelmap_raw', 'instancemap'):
             if key not in batch:
                 raise RuntimeError('test.evaluator {!r}: the batch carries no {!r}; the test loader yields it when the key is set'
                                    .format(self.evaluator, key))
-        offsets = batch.get('pad_offset') or [(0, 0)] * len(batch['border_size'])
-        records = [(int(x0), int(y0), int(bw), int(bh)) for (x0, y0), (bw, bh) in zip(offsets, batch['border_size'])]
-        self.cs_score.update(pred, batch['labelmap_raw'].to(self.device), batch['instancemap'].to(self.device), records)
+        score = self.cs_score if score is None else score
+        score.update(pred, batch['labelmap_raw'].to(self.device), batch['instancemap'].to(self.device), self._records(batch))
+
+    def _segfix(self, pred, batch):
+        """One batch of the SegFix refinement -> (refined train ids, refined dataset ids, changed pixels per image), all on the device."""
+        if 'segfix_offset' not in batch:
+            raise RuntimeError("test.segfix_offset_dir: the batch carries no 'segfix_offset'; the test loader yields it when the key is "
+                               'set')
+        return K.segfix_shift(pred, batch['segfix_offset'].to(self.device), self._records(batch), self.segfix_scale, self.segfix_lut)
 
     @torch.no_grad()
     def test(self, data_loader=None):
@@ -575,6 +641,14 @@ class Tester(object):
             self.cs_score.reset()
         K_cls = self.configer.get('data', 'num_classes')
         confusion = torch.zeros(K_cls, K_cls, dtype=torch.int64, device=self.device)
+        segfix, confusion_sf = self.segfix_dir is not None, None
+        if segfix:
+            segfix_dir = os.path.join(self.save_dir, SEGFIX_LABEL_DIR)
+            os.makedirs(segfix_dir, exist_ok=True)
+            self.running_score_segfix.reset()
+            confusion_sf = torch.zeros_like(confusion)
+            if self.cs_score_segfix is not None:
+                self.cs_score_segfix.reset()
         start, n_img, scored = time.time(), 0, False
         for batch in loader:
             inputs = batch['img']
@@ -582,6 +656,8 @@ class Tester(object):
                 if self.cs_score is not None:              # check_config has refused size_mode diverse_size
                     raise NotImplementedError('test.evaluator {!r} on a list batch: images of differing sizes are not supported'
                                               .format(self.evaluator))
+                if segfix:
+                    raise NotImplementedError('test.segfix_offset_dir on a list batch: images of differing sizes are not supported')
                 scored = self._test_ragged(batch, confusion, label_dir, n_img) or scored
                 n_img += len(inputs)
                 continue
@@ -596,6 +672,16 @@ class Tester(object):
                 scored = True
             if self.cs_score is not None:
                 self._cityscapes_update(pred, batch)
+            if segfix:                                     # the finished prediction of whatever test.mode, refined on the device
+                refined, refined_ids, changed = self._segfix(pred, batch)
+                if labels is not None:
+                    K.confusion_update(refined, labels.to(self.device), confusion_sf, ignore_index=-1)
+                if self.cs_score_segfix is not None:
+                    self._cityscapes_update(refined, batch, self.cs_score_segfix)
+                ids_np, changed = refined_ids.cpu().numpy(), changed.cpu().tolist()
+                for k, (name, (x0, y0, bw, bh)) in enumerate(zip(batch['name'], self._records(batch))):
+                    Image.fromarray(ids_np[k, y0:y0 + bh, x0:x0 + bw]).save(os.path.join(segfix_dir, '{}.png'.format(name)))
+                    Log.info('SegFix {}: {} of {} pixels changed'.format(name, changed[k], bw * bh))
             pred_np = pred.cpu().numpy()
             for k, name in enumerate(batch['name']):
                 bw, bh = batch['border_size'][k]
@@ -620,4 +706,21 @@ class Tester(object):
                 for line in CS.format_tables(*self.last_cityscapes):
                     Log.info(line)
                 Log.info('Cityscapes scores written to {}'.format(self.cs_score.write_json(self.save_dir)))
+        if segfix:
+            self.running_score_segfix.update_from_hist(confusion_sf)
+            self.running_score_segfix.reduce_scores()
+            if scored or float(self.running_score_segfix.reduced_confusion_matrix.sum()) > 0:
+                self.last_miou_segfix = float(self.running_score_segfix.get_mean_iou())
+                if get_rank() == 0:
+                    Log.info('Test mIoU (SegFix) {:.6f}\tPixel acc {:.6f}'.format(self.last_miou_segfix,
+                                                                                 float(self.running_score_segfix.get_pixel_acc())))
+            if self.cs_score_segfix is not None:
+                self.cs_score_segfix.reduce_scores()       # every rank: a collective under a process group
+                self.last_cityscapes_segfix = self.cs_score_segfix.results()
+                if get_rank() == 0:
+                    Log.info('Cityscapes scores of the SegFix refinement ({})'.format(SEGFIX_LABEL_DIR))
+                    for line in CS.format_tables(*self.last_cityscapes_segfix):
+                        Log.info(line)
+                    Log.info('Cityscapes scores of the SegFix refinement written to {}'
+                             .format(self.cs_score_segfix.write_json(self.save_dir, SEGFIX_RESULT_DIR)))
         return self.last_miou

@@ -1039,6 +1039,27 @@ int cseg_cs_eval_update(const uint8_t* pred, const uint8_t* lut, const uint8_t* 
                         uint32_t* status, cseg_stream_t stream);
 int cseg_cs_eval_reduce(const uint32_t* table, int B, int64_t* stats_i, double* stats_f, cseg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * SegFix refinement of a finished prediction (csrc/segfix.hip).  Replaces shift() of scripts/cityscapes/segfix.py:64-79 for a batch:
+ * every pixel of an image's unpadded region takes the bilinear blend of the class indices around the point its offset names, in the
+ * fp32 order of torch's CPU grid_sample (three fused multiply-adds, everything else rounded on its own), rounded half to even.
+ * B * H * W < 2^31 per call.
+ *
+ *   cseg_segfix_shift  pred [B,H,W] u8 train ids; offsets [B,H,W,2] {row offset, column offset} per pixel, fp32 (offsets_int8 = 0) or
+ *                      int8 (offsets_int8 = 1) -- equal values give equal output; records [B][4] i32 {x0, y0, bw, bh}: the region of
+ *                      image b that is refined with h = bh, w = bw (clamping at the region's edge, the padding is never read) -- given
+ *                      twice as for cseg_cs_eval_update, records_host for the checks made before the launch (a region outside the
+ *                      image or with fewer than 2 rows or columns is refused) and the same values on the device; scale multiplies
+ *                      every offset in fp32; lut [256] u8 train id -> dataset id, may be null when refined_ids is.
+ *                      refined [B,H,W] u8 (not pred itself): the refined train ids inside the regions, pred outside.
+ *                      refined_ids [B,H,W] u8 or null: lut[refined].
+ *                      changed [B] i32, zero-filled by the caller: += the pixels of image b with refined != pred (one integer atomic
+ *                      per block).  Deterministic.
+ * ------------------------------------------------------------------------------------------------ */
+int cseg_segfix_shift(const uint8_t* pred, const void* offsets, int offsets_int8, const int32_t* records_host, const int32_t* records,
+                      float scale, const uint8_t* lut, int B, int H, int W, uint8_t* refined, uint8_t* refined_ids, int32_t* changed,
+                      cseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
