@@ -5,6 +5,7 @@ import collections
 import ctypes
 
 import os
+import re
 
 import torch
 from torch.autograd import Function
@@ -2326,9 +2327,14 @@ CONV3X3_SB_WRW_PAIRS = ((256, 48),)
 def conv3x3_sb_wrw_eligible(x, dy):
     """Shapes the kernel covers (NCHW fp32, Cin % 16, Cout % 48; 64-pixel row segments, 32-pixel ones for the 16 x 32 maps of the
     384-channel branch; since round 5 any width in the f16x3 arithmetic -- the last segment of a row may be ragged)."""
+    if SPLIT_ARITH == "f16x3":
+        seg = 1
+    else:                    # bf16x6 runs the version CSEG_CONV3X3_SB_WRW_V selects, and version 1 (opt-in) has no 32-pixel segments
+        m = re.match(r"\s*([+-]?\d+)", os.environ.get("CSEG_CONV3X3_SB_WRW_V", ""))          # (read as the library reads it: atoi)
+        seg = 64 if (m and int(m.group(1)) == 1) else 32
     return (_on_device(x) and x.dtype == F32 and dy.dtype == F32 and x.is_contiguous() and dy.is_contiguous()
             and x.shape[1] % 16 == 0 and (dy.shape[1] % 48 == 0 or (dy.shape[1] % 16 == 0 and SPLIT_ARITH == "f16x3"))
-            and (x.shape[3] % 32 == 0 or SPLIT_ARITH == "f16x3"))
+            and x.shape[3] % seg == 0)
 
 
 def conv3x3_sb_wrw_wanted(x, dy):
@@ -2847,7 +2853,8 @@ def basic_block_group_ok(blocks, xs):
         return False
     for blk, x in zip(blocks, xs):
         c = blk.conv1.weight.shape[0]
-        if not (c >= 32 and blk.conv1.bn_follows and blk.conv2.bn_follows and blk.bn1.momentum is not None and blk.bn2.momentum is not None
+        # (c % 48: the grouped tile body has no four-tile form -- 64-channel blocks pass every per-block rule but not the entry point)
+        if not (c >= 32 and c % 48 == 0 and blk.conv1.bn_follows and blk.conv2.bn_follows and blk.bn1.momentum is not None and blk.bn2.momentum is not None
                 and basic_block_split_ok(x, blk.conv1.weight, blk.conv2.weight)):
             return False
     return True

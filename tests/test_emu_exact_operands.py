@@ -53,3 +53,47 @@ def test_fp32_paths(monkeypatch):
     X.run_classifier(K, CPU, X.CLS_CASES[0], False, ("dense", "zero_a"))
     X.run_classifier(K, CPU, X.CLS_WIDE_CASES[0], True, ("dense", "zero_b"))
     X.run_classifier(K, CPU, X.CLS_WIDE_CASES[1], True, ("dense",))
+
+
+# ---- the shape lattices (tests/exact_cases.py: LATTICES): the entries marked `emu`, every grouped case, the autograd corners ------------------
+@pytest.mark.parametrize("cfg", [c for c in X.LATTICES if c["emu"]], ids=X.lattice_id)
+def test_lattice(cfg, monkeypatch):
+    assert X.run_lattice(_K(monkeypatch, cfg["arith"], cfg["env"]), CPU, cfg, every=cfg["emu"]) == len(X.lattice_points(cfg)[::cfg["emu"]])
+
+
+@pytest.mark.parametrize("kind", X.LATTICE_GROUP_KINDS)          # (one kind per test: a 384-channel member costs the emulator seconds)
+@pytest.mark.parametrize("shapes", X.LATTICE_GROUPS, ids=X.LATTICE_GROUP_IDS)
+def test_lattice_grouped_launches(shapes, kind, monkeypatch):
+    X.run_group(_K(monkeypatch), CPU, shapes, (kind,))
+
+
+def test_lattice_fp32_corners(monkeypatch):
+    K = _K(monkeypatch)
+    for case in X.FP32_CONV3X3_CORNERS:
+        X.run_conv3x3_fp32(K, CPU, case, ("dense", "const"))
+    for case in X.RGB_STEM_CORNERS:
+        X.run_rgb_stem(K, CPU, case, ("dense", "const"))
+    for case in X.CLS_CORNERS:
+        X.run_classifier(K, CPU, case, False, ("dense", "const"))
+    for case in X.CLS_WIDE_CORNERS:
+        X.run_classifier(K, CPU, case, True, ("dense", "const"))
+
+
+def test_predicates_match_entry_points(monkeypatch):
+    K = _K(monkeypatch)
+    assert X.run_refusals(K, CPU, monkeypatch, X.setup) > 150
+
+
+@pytest.mark.parametrize("entry", X.AUTOGRAD_LATTICE, ids=[e[0] for e in X.AUTOGRAD_LATTICE])
+def test_autograd_lattice(entry, monkeypatch):
+    X.run_autograd_lattice(_K(monkeypatch), CPU, entry)
+
+
+@pytest.mark.parametrize("case", X.BLOCK_CORNERS)                  # (one corner per test: a 192-channel block costs the emulator seconds)
+def test_block_lattice(case, monkeypatch):
+    X.run_block_lattice(_K(monkeypatch), CPU, monkeypatch, [case], grouped=False)
+
+
+@pytest.mark.parametrize("i", range(len(X.BLOCK_GROUPS)))
+def test_block_group_lattice(i, monkeypatch):
+    X.run_block_lattice(_K(monkeypatch), CPU, monkeypatch, X.BLOCK_GROUPS[i], grouped=True)

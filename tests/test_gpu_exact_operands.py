@@ -71,3 +71,62 @@ def test_fp32_classifier(case, monkeypatch):
 def test_fp32_classifier_wide(case, monkeypatch):
     K, dev = _K(monkeypatch)
     X.run_classifier(K, dev, case, wide=True)
+
+
+# ---- the shape lattices (tests/exact_cases.py: LATTICES): every entry, every evaluation ------------------------------------------------------
+@pytest.mark.parametrize("cfg", X.LATTICES, ids=X.lattice_id)
+def test_lattice(cfg, monkeypatch):
+    K, dev = _K(monkeypatch, cfg["arith"], cfg["env"])
+    assert X.run_lattice(K, dev, cfg) == len(X.lattice_points(cfg))
+
+
+@pytest.mark.parametrize("shapes", X.LATTICE_GROUPS, ids=X.LATTICE_GROUP_IDS)
+def test_lattice_grouped_launches(shapes, monkeypatch):
+    K, dev = _K(monkeypatch)
+    X.run_group(K, dev, shapes, X.LATTICE_GROUP_KINDS)
+
+
+@pytest.mark.parametrize("case", X.FP32_CONV3X3_CORNERS)
+def test_lattice_fp32_conv3x3(case, monkeypatch):
+    K, dev = _K(monkeypatch)
+    X.run_conv3x3_fp32(K, dev, case)
+
+
+@pytest.mark.parametrize("case", X.RGB_STEM_CORNERS)
+def test_lattice_fp32_rgb_stem(case, monkeypatch):
+    K, dev = _K(monkeypatch)
+    X.run_rgb_stem(K, dev, case)
+
+
+@pytest.mark.parametrize("case", X.CLS_CORNERS)
+def test_lattice_fp32_classifier(case, monkeypatch):
+    K, dev = _K(monkeypatch)
+    X.run_classifier(K, dev, case, wide=False)
+
+
+@pytest.mark.parametrize("case", X.CLS_WIDE_CORNERS)
+def test_lattice_fp32_classifier_wide(case, monkeypatch):
+    K, dev = _K(monkeypatch)
+    X.run_classifier(K, dev, case, wide=True)
+
+
+def test_predicates_match_entry_points(monkeypatch):
+    K, dev = _K(monkeypatch)
+    assert X.run_refusals(K, dev, monkeypatch, X.setup) > 150
+
+
+@pytest.mark.parametrize("entry", X.AUTOGRAD_LATTICE, ids=[e[0] for e in X.AUTOGRAD_LATTICE])
+def test_autograd_lattice(entry, monkeypatch):
+    K, dev = _K(monkeypatch)
+    X.run_autograd_lattice(K, dev, entry)
+
+
+def test_block_lattice(monkeypatch):
+    K, dev = _K(monkeypatch)
+    X.run_block_lattice(K, dev, monkeypatch, X.BLOCK_CORNERS, grouped=False)
+
+
+@pytest.mark.parametrize("i", range(len(X.BLOCK_GROUPS)))
+def test_block_group_lattice(i, monkeypatch):
+    K, dev = _K(monkeypatch)
+    X.run_block_lattice(K, dev, monkeypatch, X.BLOCK_GROUPS[i], grouped=True)
